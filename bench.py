@@ -10,9 +10,14 @@ Steps are handed round-robin to the contexts of a vslam_pipeline (--in-flight, d
 batch in flight has its own frames, outputs and communicator; the timed region ends when every
 batch is complete.  The data is SURVEY 8(d)'s regime (--data hard) since round 5.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the kernel with the largest share of the step,
-timed with HIP events on the stream the kernels run on; `cpu_baseline` is the oracle (a CPU port
-of the reference path, single thread) timed on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, warm-up, the
+timed steps and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step computed (see dump_outputs).  Everything
+else is behind --full: `roofline` is for the kernel with the largest share of the step, timed with
+HIP events on the stream the kernels run on; `parity_in_bench` holds the timed batches to the
+oracle; `cpu_baseline` is the oracle (a CPU port of the reference path, single thread) timed on a
+bounded sample of the same workload; and, unless --no-extras, the secondary measurements (other
+arrangements, data regimes, workloads and shapes, each in a fresh process).
 
 `python bench.py --gpus N` with N > 1 and no launcher in the environment starts the N ranks itself:
 the parent (which never imports torch or touches a GPU) runs `python -m torch.distributed.run
@@ -377,6 +382,36 @@ def oracle_on_frames(frames_a, frames_b, seeds, K, H, thr, gpu_out, pair0, what)
     return base, parity
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6     # under the 64 MB a dump may take, .npy headers included
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(d, arrays, pairs, limit=DUMP_LIMIT_BYTES):
+    """Write the host copies of what the last timed step computed (the arrays a caller of the path receives, whole buffers) as
+    d/<name>.npy: float32 for float32 and 8 / 16-bit integer outputs, float64 for 32 / 64-bit integer and float64 ones (every
+    value exact).  An array with one row per frame (2 x pairs rows: frame p and frame pairs + p of pair p) or per pair keeps the
+    rows of a fixed, seeded sample of pairs -- all of them when everything fits in `limit` bytes -- whose indices go to
+    d/sample_pairs.npy.  Same arguments, same inputs, same sample: two builds compare output for output."""
+    import numpy as np
+
+    def out_dtype(a):
+        return np.dtype(np.float32 if a.dtype.itemsize <= 2 or a.dtype == np.float32 else np.float64)
+
+    rows_per_pair = {pairs: 1, 2 * pairs: 2}
+    per_pair = sum(rows_per_pair[a.shape[0]] * a[0].size * out_dtype(a).itemsize for a in arrays.values() if a.shape[0] in rows_per_pair)
+    whole = sum(a.size * out_dtype(a).itemsize for a in arrays.values() if a.shape[0] not in rows_per_pair)
+    n = min(pairs, max(1, (limit - whole) // max(per_pair, 1)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pairs, n, replace=False)) if n < pairs else np.arange(pairs)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "sample_pairs.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        if a.shape[0] == 2 * pairs:
+            a = a[np.concatenate([idx, pairs + idx])]
+        elif a.shape[0] == pairs:
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a.astype(out_dtype(a)))
+
+
 def grid_algorithmic_bytes(scope, w, h, kp):
     """Compulsory HBM bytes PER FRAME of the grid extractor's stages (4 x 4 cells, levels 0-5 of an 8-level 1.2 pyramid hold
     keypoints at 1280x720): inputs read once, outputs written once."""
@@ -443,6 +478,7 @@ def grid_workload(args):
         run(c, sl)
         pipe.commit(t)
         sl.used += 1
+        return sl
 
     if args.pmc_calibrate:   # the known-size copies and the busy-pipe kernel the counter summaries calibrate against
         a_ = torch.empty(1 << 30, dtype=torch.uint8, device=dev).random_(0, 255)
@@ -466,7 +502,7 @@ def grid_workload(args):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k)
+        last = step(k)
     pipe.drain()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
@@ -475,6 +511,8 @@ def grid_workload(args):
     for sl in used:
         sl.host = {k: v.cpu().numpy() for k, v in list(sl.g.items()) + list(sl.m.items())}
         assert (sl.host["n"] > 1000).all() and (sl.host["best"][:, 0] >= 0).all() and (sl.host["best"][:, 3] >= 8).all(), "bench output degenerate"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.host, P)
     n_kp = np.concatenate([sl.host["n"] for sl in used])
     best = np.concatenate([sl.host["best"] for sl in used])
     data_label = {"easy": "easy data: translated texture + one moving block",
@@ -492,7 +530,7 @@ def grid_workload(args):
         "workspace_bytes": pipe.workspace_bytes(), "workspace_bytes_per_context": ctx.workspace_bytes(),
     }
     exit_code = 0
-    if not args.no_profile_pass:   # per-stage times, HIP events on the stream, one context, one batch after the other
+    if args.full and not args.no_profile_pass:   # per-stage times, HIP events on the stream, one context, one batch after the other
         s0 = slots[0]
         psteps = 3
         # the extractor alone (what tools/grid_bench.py times)
@@ -530,38 +568,39 @@ def grid_workload(args):
                                   "frac": top["alg_GBps"] / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": top["ms_per_launch"],
                                   "note": "stage of the grid extractor with the largest share of the step; algorithmic bytes as "
                                           "grid_algorithmic_bytes() states them; the FAST stage is bound by its vector arithmetic, not by bandwidth"}
-    # parity of what was timed + CPU baseline: the oracle on the very frames the device processed
-    n_chk = min(P, args.cpu_pairs if args.cpu_pairs > 0 else 2, 8)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from oracle_lib import Oracle
-    o = Oracle()
-    patn = synth.brief_pattern()
-    sl = used[0]
-    fa, fb = sl.bgr[:n_chk].cpu().numpy(), sl.bgr[P:P + n_chk].cpu().numpy()
-    bad = []
-    t1 = time.perf_counter()
-    for p_ in range(n_chk):
-        ra = o.extract_features_grid(fa[p_], GRID[0], GRID[1], patn)
-        rb = o.extract_features_grid(fb[p_], GRID[0], GRID[1], patn)
-        ref = o.match_features(ra[1], ra[2], rb[1], rb[2], int(sl.seeds_np[p_]) & 0xFFFFFFFF, H, thr)
-        na, nb, k = len(ra[1]), len(rb[1]), len(ref["matches"])
-        ho = sl.host
-        ok = (int(ho["n"][p_]) == na and int(ho["n"][P + p_]) == nb and np.array_equal(ho["xy"][p_, :na].view(np.uint32), ra[1].view(np.uint32))
-              and np.array_equal(ho["desc"][p_, :na], ra[2]) and np.array_equal(ho["desc"][P + p_, :nb], rb[2])
-              and int(ho["best"][p_, 3]) == k and np.array_equal(ho["matches"][p_, :k], ref["matches"])
-              and np.array_equal(ho["F"][p_].view(np.uint32), np.asarray(ref["F"], np.float32).reshape(-1).view(np.uint32)))
-        if not ok:
-            bad.append(p_)
-    secs = time.perf_counter() - t1
-    result["parity_in_bench"] = {"pairs": n_chk, "bit_exact": not bad,
-                                 "checked": "keypoint counts, coordinates and descriptors of both frames (grid extractor), inlier-match lists and F (as "
-                                            "uint32) of the timed steps' output vs the oracle on the same bytes"}
-    if bad:
-        result["parity_in_bench"]["mismatching_pairs"] = bad
-        exit_code = 3
-    if args.cpu_pairs > 0:
-        result["cpu_baseline"] = {"value": n_chk / secs, "unit": "frame-pairs/s", "cores": 1, "kind": "port",
-                                  "sample": f"{n_chk} pairs of the timed batch copied back from the device, oracle single thread, {secs:.1f} s"}
+    if args.full:
+        # parity of what was timed + CPU baseline: the oracle on the very frames the device processed
+        n_chk = min(P, args.cpu_pairs if args.cpu_pairs > 0 else 2, 8)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from oracle_lib import Oracle
+        o = Oracle()
+        patn = synth.brief_pattern()
+        sl = used[0]
+        fa, fb = sl.bgr[:n_chk].cpu().numpy(), sl.bgr[P:P + n_chk].cpu().numpy()
+        bad = []
+        t1 = time.perf_counter()
+        for p_ in range(n_chk):
+            ra = o.extract_features_grid(fa[p_], GRID[0], GRID[1], patn)
+            rb = o.extract_features_grid(fb[p_], GRID[0], GRID[1], patn)
+            ref = o.match_features(ra[1], ra[2], rb[1], rb[2], int(sl.seeds_np[p_]) & 0xFFFFFFFF, H, thr)
+            na, nb, k = len(ra[1]), len(rb[1]), len(ref["matches"])
+            ho = sl.host
+            ok = (int(ho["n"][p_]) == na and int(ho["n"][P + p_]) == nb and np.array_equal(ho["xy"][p_, :na].view(np.uint32), ra[1].view(np.uint32))
+                  and np.array_equal(ho["desc"][p_, :na], ra[2]) and np.array_equal(ho["desc"][P + p_, :nb], rb[2])
+                  and int(ho["best"][p_, 3]) == k and np.array_equal(ho["matches"][p_, :k], ref["matches"])
+                  and np.array_equal(ho["F"][p_].view(np.uint32), np.asarray(ref["F"], np.float32).reshape(-1).view(np.uint32)))
+            if not ok:
+                bad.append(p_)
+        secs = time.perf_counter() - t1
+        result["parity_in_bench"] = {"pairs": n_chk, "bit_exact": not bad,
+                                     "checked": "keypoint counts, coordinates and descriptors of both frames (grid extractor), inlier-match lists and F (as "
+                                                "uint32) of the timed steps' output vs the oracle on the same bytes"}
+        if bad:
+            result["parity_in_bench"]["mismatching_pairs"] = bad
+            exit_code = 3
+        if args.cpu_pairs > 0:
+            result["cpu_baseline"] = {"value": n_chk / secs, "unit": "frame-pairs/s", "cores": 1, "kind": "port",
+                                      "sample": f"{n_chk} pairs of the timed batch copied back from the device, oracle single thread, {secs:.1f} s"}
     pipe.close()
     sys.stdout.flush()
     os.write(real_stdout, (json.dumps(result) + "\n").encode())
@@ -712,6 +751,13 @@ def main():
                     help="wall-clock limit in seconds for the ranks this process starts itself (--gpus N > 1 without a launcher)")
     ap.add_argument("--pmc-calibrate", action="store_true",
                     help="also run two 1 GiB streaming copies (4 B and 16 B per lane) so FETCH_SIZE/WRITE_SIZE can be calibrated")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the per-kernel pass and rooflines, the oracle's "
+                         "parity check of the timed batches and the CPU baselines (--cpu-pairs, --cpu-all-cores-pairs) and, unless "
+                         "--no-extras, the secondary measurements; without it a run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's output arrays) as DIR/<name>.npy in float32 / "
+                         "float64, a fixed seeded sample of the pairs where the whole would exceed 60 MB (DIR/sample_pairs.npy: which)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -829,6 +875,7 @@ def main():
             pipe.wait(t)
             sl.gathered.copy_(shard.gather_records(sl.rec.cpu(), world, n_items=world * P))
         sl.used += 1
+        return sl
 
     if args.pmc_calibrate and rank == 0:
         a = torch.empty(1 << 30, dtype=torch.uint8, device=dev).random_(0, 255)
@@ -858,7 +905,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k)
+        last = step(k)
     pipe.drain()                 # every batch complete, its gather included (same stream, in front of the batch's event)
     torch.cuda.synchronize(dev)
     if multi:
@@ -887,7 +934,8 @@ def main():
         flag = torch.tensor([1 if gather_ok else 0])
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         gather_ok = bool(flag.item())
-    host_out = used[0].host
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.out.items()}, P)
     best = np.concatenate([sl.host["best"] for sl in used])
     n_kp = np.concatenate([sl.host["n"] for sl in used])
 
@@ -990,7 +1038,7 @@ def main():
                 "arithmetic": mv}
 
     # ---- separate pass: per-kernel durations with HIP events on the kernels' own stream (context 0, its own batch)
-    if rank == 0 and not args.no_profile_pass:
+    if rank == 0 and args.full and not args.no_profile_pass:
         s0 = slots[0]
         psteps = max(1, min(3, args.steps))
         rep = profile_pass(ctx, s0.bgr, P, K, H, s0.seeds, psteps)
@@ -1080,7 +1128,7 @@ def main():
                                                   "per step with the batches in flight"}
 
     # ---- the oracle on the timed batches' own bytes: parity of what was timed -- a share from EVERY context -- and the CPU baseline
-    if rank == 0:
+    if rank == 0 and args.full:
         n_cpu = min(P * len(used), args.cpu_pairs if (world == 1 and args.cpu_pairs > 0) else 4)
         share = [n_cpu // len(used) + (1 if i < n_cpu % len(used) else 0) for i in range(len(used))]
         pairs_done, secs, bad, per_ctx = 0, 0.0, [], []
@@ -1108,7 +1156,7 @@ def main():
 
     # ---- secondary measurements (rank 0, one GPU): one context, the in-flight sweep, the other data regime, the
     # full-evaluation worst case, the other workloads with their own per-kernel pass
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         try:
             s0 = slots[0]
 
@@ -1119,7 +1167,7 @@ def main():
                 times out, exits non-zero or prints no line comes back as {"failed": True, ...} with the tail of its stderr (a parity
                 mismatch -- exit code 3 -- still carries its line under "line")."""
                 import subprocess
-                cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extras", "--cpu-pairs", "0", "--cpu-all-cores-pairs", "0",
+                cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extras", "--cpu-pairs", "0", "--cpu-all-cores-pairs", "0",
                        "--data", args.data, "--solver", args.solver] + extra
                 env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VSLAM_BENCH_FORCE_DIST")}
                 try:

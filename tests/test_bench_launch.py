@@ -106,7 +106,7 @@ def test_the_n_gt_1_path_with_one_rccl_rank(comm):
     s.close()
     env = dict(os.environ, VSLAM_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-extras",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--full", "--no-extras",
                         "--no-profile-pass", "--cpu-pairs", "8", "--cpu-all-cores-pairs", "0", "--pairs", "32", "--comm", comm],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -17,7 +17,7 @@ for lib in libs:
     if lib:
         env["VSLAM_AMD_LIB"] = os.path.abspath(lib)
         env["VSLAM_BENCH_ALLOW_DEGENERATE"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--cpu-pairs", "0",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full", "--cpu-pairs", "0",
                         "--cpu-all-cores-pairs", "0", "--no-extras"], env=env, capture_output=True, text=True)
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if not line:

@@ -6,7 +6,7 @@ export VSLAM_AMD_LIB=${VSLAM_AMD_LIB:-$(dirname $0)/../vslam_amd/libvslam_amd_ex
 run() {   # label, then VAR=value ...
   label=$1; shift
   for wl in C3 C5; do
-    env "$@" timeout -k 10 300 python bench.py --workload $wl --steps 20 --warmup 3 --cpu-pairs 4 --cpu-all-cores-pairs 0 --no-extras \
+    env "$@" timeout -k 10 300 python bench.py --workload $wl --steps 20 --warmup 3 --full --cpu-pairs 4 --cpu-all-cores-pairs 0 --no-extras \
       2>/dev/null > /tmp/ab_match.json
     python - "$wl" "$label" <<'P'
 import json, sys
