@@ -134,6 +134,7 @@ extern "C" int vso_associate_map_points(const float *map_points /*N x 4*/, int n
                                         const uint8_t *kp_desc, int n_kp, const int32_t *obs_offsets,
                                         const uint8_t *obs_desc, float radius, uint32_t dist_threshold,
                                         int32_t *map_point_ids, int32_t *out_claim) {
+    std::vector<int32_t> hits;
     for (int i = 0; i < n_map; i++) {
         out_claim[i] = -1;
         const float *P = map_points + (size_t)i * 4;
@@ -146,9 +147,9 @@ extern "C" int vso_associate_map_points(const float *map_points /*N x 4*/, int n
         const float hh = pr[2];
         const float x = pr[0] / hh, y = pr[1] / hh;                       // src/vslam.cpp:136-140
         if (!(x >= 0 && x < img_w && y >= 0 && y < img_h)) continue;      // :141-143
-        int32_t hits[256];
-        int cnt = vso_kdtree_radius_frame(kd_nodes, kp_xy, n_kp, x, y, radius, hits, 256);   // :149
-        if (cnt > 256) cnt = 256;
+        // radius_search returns every hit (src/KDTree.cpp:145-149): a keypoint is at most one hit, so n_kp slots hold them all
+        hits.resize(n_kp > 0 ? n_kp : 1);
+        const int cnt = vso_kdtree_radius_frame(kd_nodes, kp_xy, n_kp, x, y, radius, hits.data(), n_kp);   // :149
         for (int h = 0; h < cnt; h++) {
             const int idx = hits[h];
             if (map_point_ids[idx] >= 0) continue;                         // :151

@@ -4,12 +4,16 @@ keypoint.  Cases mix keypoint layouts (random, one-pixel lattices where every ma
 sizes from 0 to several thousand per item, descriptor regimes (all acceptable / mostly rejected / a mix), 0-3 stored
 observations per map point, keypoints already assigned before the call, and items of different sizes in one batch.
 
+Every item is also held to the float64 definition of tests/ref64.py; an item with a borderline projection or radius decision
+keeps only the oracle comparison and is counted in `stats`.
 `python tests/fuzz_assoc.py SEED SECONDS` runs it for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
 import sys
 import time
 
 import numpy as np
 import torch
+
+import ref64
 
 
 def _item(o, rng, w, h):
@@ -56,7 +60,8 @@ def _item(o, rng, w, h):
     return dict(kp=kp, desc=desc, nodes=o.kdtree_build_frame(kp), mp=mp, offs=offs, od=od, ids=ids)
 
 
-def run(ctx, o, seed, cases=None, seconds=None):
+def run(ctx, o, seed, cases=None, seconds=None, stats=None):
+    stats = {} if stats is None else stats
     rng = np.random.default_rng(seed)
     t0, done = time.time(), 0
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -90,6 +95,10 @@ def run(ctx, o, seed, cases=None, seconds=None):
             tag = (seed, done, b, w, h, k, m, radius)
             assert np.array_equal(claim[b, :m], ref_claim), ("claims",) + tag
             assert np.array_equal(got[b, :k], ref_ids), ("map_point_ids",) + tag
+            held = ref64.hold_association(s["mp"], c2, w, h, s["nodes"], s["kp"], s["desc"], s["offs"], s["od"], s["ids"], got[b, :k],
+                                          claim[b, :m], radius=radius)
+            key = "held" if held else "undecided"
+            stats[key] = stats.get(key, 0) + 1
         done += 1
     return done
 

@@ -5,12 +5,16 @@
   * triangulate (the declared signature, any two camera matrices) on point pairs consistent with the cameras, perturbed, coincident,
     at the principal point, far outside the image;
   * the reprojection filter on what comes out, with some matches already carrying a map point id.
+Every case is also held to the float64 definitions of tests/ref64.py; what ref64 marks undecided (rank < 2, a trace or t_z at
+0, a point at infinity, a filter decision on the threshold) keeps only the oracle comparison and is counted in `stats`.
 `python tests/fuzz_pose.py SEED SECONDS` runs it for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
 import sys
 import time
 
 import numpy as np
 import torch
+
+import ref64
 
 bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
 
@@ -22,7 +26,8 @@ def _rot(rng, deg):
             np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
 
 
-def run(ctx, o, seed, cases=None, seconds=None):
+def run(ctx, o, seed, cases=None, seconds=None, stats=None):
+    stats = {} if stats is None else stats
     rng = np.random.default_rng(seed)
     t0, done = time.time(), 0
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -85,6 +90,9 @@ def run(ctx, o, seed, cases=None, seconds=None):
             Rr, tr = o.extract_Rt(Fs[b], K)
             assert np.array_equal(bits(R[b]), bits(Rr.reshape(9))) and np.array_equal(bits(tv[b]), bits(tr)), ("extract_Rt", seed, done, b)
             assert np.array_equal(bits(c2[b]), bits(o.camera_matrix(K, Rr, tr).reshape(12))), ("camera matrix", seed, done, b)
+            st = ref64.hold_pose(Fs[b], K, R[b], tv[b], c2[b])
+            stats["rt"] = stats.get("rt", 0) + st["rt"]
+            stats["rt_undecided"] = stats.get("rt_undecided", 0) + 1 - st["rt"]
         ref = o.triangulate(p1, p2, c1, c2m)
         assert np.array_equal(bits(pts.cpu().numpy()), bits(ref)), ("triangulate", seed, done, n, mode)
         assert np.array_equal(bits(pts_chain.cpu().numpy()[0, :n]), bits(ref)), ("triangulate (chain form)", seed, done, n, mode)
@@ -92,6 +100,19 @@ def run(ctx, o, seed, cases=None, seconds=None):
         assert int(rn.cpu().numpy()[0]) == len(kept) and np.array_equal(ridx.cpu().numpy()[0, :len(kept)], kept), ("filter", seed, done, n, mode)
         e = float(rerr.cpu().numpy()[0])
         assert e == err or (np.isnan(e) and np.isnan(err)), ("filter error sum", seed, done, e, err)
+        tri = ref64.triangulate(p1, p2, c1, c2m)                      # the declared form with any two cameras
+        ok = ~tri["at_inf"] & (tri["tol"] < 1e-2)
+        assert (ref64.homogeneous_error(pts.cpu().numpy(), tri)[ok] <= tri["tol"][ok]).all(), ("triangulate vs ref64", seed, done)
+        fr = ref64.reprojection_filter(pts_chain.cpu().numpy()[0, :n], p1, p2, c1, c2m, ids, 4.0)
+        dec = fr["per"] > 1
+        got = np.zeros(n, bool); got[ridx.cpu().numpy()[0, :int(rn.cpu().numpy()[0])]] = True
+        want = np.zeros(n, bool); want[fr["kept"]] = True
+        assert np.array_equal(got[dec], want[dec]), ("filter vs ref64", seed, done)
+        if dec.all():
+            assert abs(e - fr["err"]) <= fr["err_tol"], ("filter error sum vs ref64", seed, done, e, fr["err"])
+        for k, v in (("points", int(ok.sum())), ("points_undecided", int((~ok).sum())), ("filter", int(dec.sum())),
+                     ("filter_undecided", int((~dec).sum()))):
+            stats[k] = stats.get(k, 0) + v
         done += 1
     return done
 

@@ -1,10 +1,15 @@
 """Map association (src/vslam.cpp:129-161 + orb_distance) on the device vs the oracle: the claimed
-keypoint of every map point and the updated map_point_ids, bit-exact, including contended keypoints."""
+keypoint of every map point and the updated map_point_ids, bit-exact, including contended keypoints; and the same
+outputs held to the float64 restatement of tests/ref64.py wherever a scene has no borderline decision."""
 import numpy as np
 import pytest
 import torch
 
-from vslam_amd import synth
+import ref64
+import test_oracle_assoc as scenes
+from vslam_amd import capi
+
+VSLAM_MAX_KP = 16384   # include/vslam_amd.h
 
 pytestmark = pytest.mark.gpu
 
@@ -62,14 +67,17 @@ def test_association_bit_exact(ctx, oracle):
     claim = ctx.associate(t(mp), t(nm), t(c2), w, h, t(nodes), t(xy), t(desc), t(n), t(offs), t(od), d_ids)
     ctx.synchronize()
     claim, got_ids = claim.cpu().numpy(), d_ids.cpu().numpy()
-    total = 0
+    total = held = 0
     for b, s in enumerate(items):
         k, m = len(s["kp"]), len(s["mp"])
         ref_ids, ref_claim = oracle.associate(s["mp"], s["c2"], w, h, s["nodes"], s["kp"], s["desc"], s["offs"], s["od"], s["ids"])
         assert np.array_equal(claim[b, :m], ref_claim), b
         assert np.array_equal(got_ids[b, :k], ref_ids), b
         total += int((ref_claim >= 0).sum())
+        held += ref64.hold_association(s["mp"], s["c2"], w, h, s["nodes"], s["kp"], s["desc"], s["offs"], s["od"], s["ids"],
+                                       got_ids[b, :k], claim[b, :m])
     assert total > 300, "scenario should produce associations"
+    assert held >= 2, "the scenes should be free of borderline decisions"
 
 
 def test_association_edge_cases(ctx, oracle):
@@ -91,6 +99,7 @@ def test_association_edge_cases(ctx, oracle):
         "out of view": (np.stack([Kinv(kp[i] + 5000, 4.0) for i in range(8)]), np.arange(9, dtype=np.int32), np.repeat(desc[:8], 1, 0)),
         "behind one keypoint": (same, np.arange(7, dtype=np.int32), np.repeat(desc[5:6], 6, 0)),
     }
+    held = 0
     for name, (mp, offs, od) in cases.items():
         ids = np.full(n_kp, -1, np.int32)
         B, Mp, Os = 1, max(len(mp), 1), len(od)
@@ -104,10 +113,13 @@ def test_association_edge_cases(ctx, oracle):
         ref_ids, ref_claim = oracle.associate(mp, c2, w, h, nodes, kp, desc, offs, od, ids)
         assert np.array_equal(claim.cpu().numpy()[0, :len(mp)], ref_claim), name
         assert np.array_equal(d_ids.cpu().numpy()[0], ref_ids), name
+        held += ref64.hold_association(mp, c2, w, h, nodes, kp, desc, offs, od, ids, d_ids.cpu().numpy()[0],
+                                       claim.cpu().numpy()[0, :len(mp)])
         if name == "behind one keypoint":
             assert ref_claim[0] == 5 and (ref_claim[1:] == -1).all()
         elif name != "empty map":
             assert (ref_claim == -1).all(), name
+    assert held >= 3, "projections that land on a keypoint exactly 2 px from another are the only borderline ones here"
 
 
 @pytest.mark.parametrize("radius,fill", [(2.0, 0.0), (2.05, 0.3), (2.05, 0.7)])
@@ -150,11 +162,111 @@ def test_association_long_claim_chains(ctx, oracle, radius, fill):
                           t(offb), t(odb), d_ids, radius=radius)
     ctx.synchronize()
     claim, got = claim.cpu().numpy(), d_ids.cpu().numpy()
-    later = 0
+    later = held = 0
     for b, (mp, offs, od, ids) in enumerate(items):
         ref_ids, ref_claim = oracle.associate(mp, c2, w, h, nodes, kp, desc, offs, od, ids, radius=radius)
         assert np.array_equal(claim[b, :len(mp)], ref_claim), b
         assert np.array_equal(got[b], ref_ids), b
         later += int((ref_claim >= 0).sum())
+        held += ref64.hold_association(mp, c2, w, h, nodes, kp, desc, offs, od, ids, got[b], claim[b, :len(mp)], radius=radius)
     free = int((items[0][3] < 0).sum())
     assert (claim[0, :4000] >= 0).sum() > 0.9 * free, "the big item should use up nearly every free keypoint"
+    assert held >= 1, "the small lattice scenes should be free of borderline decisions"
+
+
+def _run(ctx, items, kp_stride=None):
+    """Associate a batch of scenes (tests/test_oracle_assoc.py builders) on the device; returns (claims, ids) per item."""
+    B = len(items)
+    Kp = kp_stride or max(len(s["kp"]) for s in items)
+    Mp = max(len(s["mp"]) for s in items)
+    Os = max(len(s["od"]) for s in items)
+    xy = np.zeros((B, Kp, 2), np.float32); desc = np.zeros((B, Kp, 32), np.uint8); nodes = np.zeros((B, Kp), np.int32)
+    n = np.zeros(B, np.int32); mp = np.zeros((B, Mp, 4), np.float32); nm = np.zeros(B, np.int32)
+    offs = np.zeros((B, Mp + 1), np.int32); od = np.zeros((B, Os, 32), np.uint8); ids = np.full((B, Kp), -1, np.int32)
+    c2 = np.zeros((B, 12), np.float32)
+    assert len({(s["w"], s["h"], s["radius"]) for s in items}) == 1
+    for b, s in enumerate(items):
+        k, m = len(s["kp"]), len(s["mp"])
+        xy[b, :k], desc[b, :k], nodes[b, :k], n[b] = s["kp"], s["desc"], s["nodes"], k
+        mp[b, :m], nm[b], offs[b, :m + 1], od[b, :len(s["od"])] = s["mp"], m, s["offs"], s["od"]
+        offs[b, m + 1:] = s["offs"][-1]
+        ids[b, :k], c2[b] = s["ids"], s["c2"].reshape(12)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d_ids = t(ids)
+    claim = ctx.associate(t(mp), t(nm), t(c2), items[0]["w"], items[0]["h"], t(nodes), t(xy), t(desc), t(n), t(offs), t(od), d_ids,
+                          radius=items[0]["radius"])
+    return claim, d_ids
+
+
+def _held(oracle, items, claim, d_ids):
+    claim, got = claim.cpu().numpy(), d_ids.cpu().numpy()
+    for b, s in enumerate(items):
+        k, m = len(s["kp"]), len(s["mp"])
+        ref_ids, ref_claim = scenes.run_oracle(oracle, s)
+        assert np.array_equal(claim[b, :m], ref_claim) and np.array_equal(got[b, :k], ref_ids), b
+        r = scenes.run_ref(s)
+        assert r["slack"] > 1, b
+        assert np.array_equal(claim[b, :m], r["claim"]) and np.array_equal(got[b, :k], r["ids"]), b
+    return claim, got
+
+
+def test_association_at_max_kp_stride(ctx, oracle):
+    """kp_stride = VSLAM_MAX_KP = 16384: the resolve kernel's LDS (a bit and an owner word per keypoint slot) is 67584 B, past
+    the 64 KB a launch gets without opting in.  A full 128 x 128 lattice of keypoints and a small item share the batch."""
+    w, h = 256, 256
+    rng = np.random.default_rng(16384)
+    gx, gy = np.meshgrid(np.arange(64, 192), np.arange(64, 192))
+    kp = np.stack([gx.ravel(), gy.ravel()], 1).astype(np.float32)
+    rng.shuffle(kp)
+    assert len(kp) == 16384
+    proto = rng.integers(0, 256, 32, dtype=np.uint8)
+    desc = np.repeat(proto[None], len(kp), 0)
+    desc[:, 3] ^= rng.integers(0, 256, len(kp), dtype=np.uint8)
+    px = np.stack([rng.uniform(60, 196, 1700), rng.uniform(60, 196, 1700)], 1)
+    px = px[scenes.clear_of_circles(px, kp, 2.0)][:1500]   # no radius decision on a boundary
+    n_map = len(px)
+    big = dict(kp=kp, desc=desc, nodes=oracle.kdtree_build_frame(kp), c2=scenes._c2(w, h),
+               mp=scenes._back(px, rng.uniform(2, 6, n_map), w, h), offs=np.arange(n_map + 1, dtype=np.int32),
+               od=np.repeat(proto[None], n_map, 0), ids=np.where(rng.random(len(kp)) < 0.2, 9, -1).astype(np.int32), w=w, h=h,
+               radius=2.0)
+    small = scenes.random_scene(oracle, 2, w, h, n_kp=400, n_map=90)
+    claim, d_ids = _run(ctx, [big, small], kp_stride=VSLAM_MAX_KP)
+    ctx.synchronize()
+    claim, _ = _held(oracle, [big, small], claim, d_ids)
+    assert (claim[0, :n_map] >= 0).sum() > 1000
+
+
+def test_association_more_than_256_radius_hits(ctx, oracle):
+    """~300 keypoints in range of one map point, the only acceptable one after the 256th hit: it is claimed."""
+    s = scenes.many_hits_scene(oracle)
+    claim, d_ids = _run(ctx, [s])
+    ctx.synchronize()
+    claim, _ = _held(oracle, [s], claim, d_ids)
+    assert claim[0, 0] == s["target"]
+
+
+def test_association_16_acceptable_hits_and_the_17th(ctx, oracle):
+    """The documented contract (include/vslam_amd.h): 16 acceptable hits per map point are kept and the result is exact; a
+    17th makes vslam_ctx_synchronize report VSLAM_ERR_CAPACITY (and clears it)."""
+    s16 = scenes.acceptable_hits_scene(oracle, 16)
+    claim, d_ids = _run(ctx, [s16])
+    ctx.synchronize()
+    claim, _ = _held(oracle, [s16], claim, d_ids)
+    assert claim[0, 0] == s16["target"]
+    s17 = scenes.acceptable_hits_scene(oracle, 17)
+    _run(ctx, [s17])
+    with pytest.raises(capi.VslamError, match="CAPACITY"):
+        ctx.synchronize()
+    ctx.synchronize()                                   # the flag was cleared
+
+
+def test_association_exact_ties(ctx, oracle):
+    """x == W is out of view, x == 0 in; d^2 == r^2 is no hit; orb_distance is the minimum; a distance of exactly 64 is
+    rejected -- on the device, with every value exact."""
+    s = scenes.exact_scene()
+    s["nodes"] = oracle.kdtree_build_frame(s["kp"])
+    claim, d_ids = _run(ctx, [s])
+    ctx.synchronize()
+    assert list(claim.cpu().numpy()[0]) == s["expect"]
+    r = scenes.run_ref(s)
+    assert np.array_equal(d_ids.cpu().numpy()[0], r["ids"])

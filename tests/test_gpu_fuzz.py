@@ -28,9 +28,13 @@ def test_grid_extractor_on_random_shapes_grids_and_content(ctx, oracle):
 
 def test_fuzz_assoc_slice(ctx, oracle):
     import fuzz_assoc
-    assert fuzz_assoc.run(ctx, oracle, seed=20261009, cases=40) == 40
+    stats = {}
+    assert fuzz_assoc.run(ctx, oracle, seed=20261009, cases=40, stats=stats) == 40
+    assert stats.get("held", 0) > stats.get("undecided", 0), stats      # most items are held to tests/ref64.py as well
 
 
 def test_fuzz_pose_slice(ctx, oracle):
     import fuzz_pose
-    assert fuzz_pose.run(ctx, oracle, seed=20261010, cases=60) == 60
+    stats = {}
+    assert fuzz_pose.run(ctx, oracle, seed=20261010, cases=60, stats=stats) == 60
+    assert stats["rt"] > 300 and stats["points"] > 3000 and stats["filter"] > 3000, stats   # held to tests/ref64.py as well

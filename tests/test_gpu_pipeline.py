@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import ref64
 from vslam_amd import build, capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -301,6 +302,15 @@ def test_pose_chain_as_tickets(ctx):
         ctx.synchronize()
         refs.append({k: v.cpu().numpy() for k, v in o.items()})
     assert sum(int(r["n_inliers"].sum()) for r in refs) > 50, "the scenes should triangulate"
+    for ref in refs:                   # the outputs the tickets must reproduce, held to the float64 definitions (tests/ref64.py)
+        for b in range(P):
+            if ref["best"][b, 0] < 0:
+                continue
+            m, ni = int(ref["best"][b, 3]), int(ref["n_inliers"][b])
+            mm = ref["matches"][b, :m]
+            p1, p2 = ref["xy"][b][mm[:, 0]], ref["xy"][P + b][mm[:, 1]]
+            ref64.hold_pose(ref["F"][b], Kmat, ref["R"][b], ref["t"][b], ref["c2"][b], p1, p2, ref["points4d"][b, :m],
+                            np.full(m, -1, np.int32), ref["inlier_idx"][b, :ni], ref["error"][b])
 
     def same(out, ref, tag):   # what a batch defines: rows up to its counts (the buffers are reused by later tickets)
         g = {k: v.cpu().numpy() for k, v in out.items()}

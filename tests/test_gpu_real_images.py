@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import ref64
 from vslam_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -180,6 +181,8 @@ def test_pose_chain_on_photographs(ctx, oracle, real):
         assert np.array_equal(bits(pts[b, :k]), bits(ref)), b
         kept, err = oracle.reprojection_filter(ref, p1, p2, c1, c2r, ids[b, :k], 4.0)
         assert rn[b] == len(kept) and np.array_equal(ridx[b, :rn[b]], kept) and rerr[b] == err, b
+        # and the device's outputs against the float64 definition of each stage (tests/ref64.py)
+        ref64.hold_pose(o["F"][b], Kmat, R[b], tv[b], c2[b], p1, p2, pts[b, :k], ids[b, :k], ridx[b, :rn[b]], rerr[b])
 
 
 def test_chained_pose_entry_on_photographs(ctx, oracle, real):
@@ -216,6 +219,8 @@ def test_chained_pose_entry_on_photographs(ctx, oracle, real):
         assert np.array_equal(bits(o["points4d"][b, :k]), bits(ref)), b
         kept, err = oracle.reprojection_filter(ref, p1, p2, c1, c2r, np.full(k, -1, np.int32), 4.0)
         assert o["n_inliers"][b] == len(kept) and np.array_equal(o["inlier_idx"][b, :len(kept)], kept) and o["error"][b] == err, b
+        ref64.hold_pose(o["F"][b], Kmat, o["R"][b], o["t"][b], o["c2"][b], p1, p2, o["points4d"][b, :k], np.full(k, -1, np.int32),
+                        o["inlier_idx"][b, :o["n_inliers"][b]], o["error"][b])
 
 
 def test_triangulate_points_generic_form(ctx, oracle):
