@@ -124,6 +124,12 @@ int vso_resize_linear_exact(const uint8_t *src, int sw, int sh, uint8_t *dst, in
  * 6 floats per keypoint (x, y, size, angle, response, octave) */
 int vso_orb_detect(const uint8_t *gray, int w, int h, int nfeatures, int fast_threshold, float *out_kp,
                    int cap, int32_t *out_n);
+/* read-only views of detect's intermediates: the pyramid without its reflect frame (level l is sizes[2l] x sizes[2l+1],
+ * packed; -2 when cap bytes do not hold it), nfeaturesPerLevel, the centroid disc's umax[0..half], fastAtan2 elementwise */
+int vso_orb_pyramid(const uint8_t *gray, int w, int h, int nlevels, uint8_t *out, int64_t cap, int32_t *sizes);
+int vso_orb_level_budget(int nfeatures, int nlevels, int32_t *out);
+int vso_orb_umax(int half, int32_t *out);
+int vso_fast_atan2(const float *y, const float *x, int n, float *out);
 /* extract_features(Frame&, nrows, ncols): src/Frame.cpp:16-51.  bgr is modified (:32). */
 int vso_extract_features_grid(uint8_t *bgr, int w, int h, int stride, int nrows, int ncols,
                               const int8_t *pattern, float *out_xy, uint8_t *out_desc,

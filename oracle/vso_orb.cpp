@@ -3,7 +3,7 @@
 // Follows /root/reference/src/Frame.cpp:16-51 (the grid ORB/FAST extractor; its only call site is
 // commented out at src/vslam.cpp:63, but it is the "ORB/FAST" the north star names):
 //   per cell (columns outer, rows inner): cv::rectangle(image, cell, black) :32;
-//   ORB(500, 1.2, 8, 31, 0, 2, HARRIS_SCORE, 31, fastThreshold 20)->detect(cell) :33;
+//   ORB(500, 1.2f, 8, 31, 0, 2, HARRIS_SCORE, 31, fastThreshold 20)->detect(cell) :33;
 //   if fewer than 500: the fastThreshold-5 detector's result REPLACES it :34-36;
 //   keypoints shifted by the cell origin :37-40; then ORB::compute(whole image, all keypoints) :43.
 // Everything below the loop is OpenCV-internal and restated from OpenCV 4.x's published code
@@ -59,6 +59,10 @@ void sincos_deg_pinned(float angle_deg, float *s_out, float *c_out) {
 }  // namespace vso
 
 namespace {
+
+// ORB::create takes scaleFactor as a float and src/Frame.cpp:23-24 passes 1.2f: every level scale is
+// (float)pow((double)1.2f, l), which differs from (float)pow(1.2, l) in the last bit from level 3 on
+constexpr double kScaleFactor = (double)1.2f;
 
 struct KeyPt {
     float x, y, size, angle, response;
@@ -362,12 +366,9 @@ void ic_angles(const Pyramid &P, std::vector<KeyPt> &pts, const std::vector<int>
 }
 
 // ---------------------------------------------------------------- ORB::detect (computeKeyPoints)
-void orb_detect(const uint8_t *gray, int w, int h, int step, int nfeatures, double scaleFactor, int nlevels,
-                int edgeThreshold, int patchSize, int fastThreshold, std::vector<KeyPt> &all) {
-    all.clear();
-    Pyramid P;
-    build_pyramid(gray, w, h, step, nlevels, scaleFactor, P);
-    std::vector<int> per_level(nlevels);
+// nfeaturesPerLevel: geometric in 1 / scaleFactor, the remainder on the last level
+void level_budget(int nfeatures, double scaleFactor, int nlevels, std::vector<int> &per_level) {
+    per_level.assign(nlevels, 0);
     const float factor = (float)(1.0 / scaleFactor);
     float ndesired = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
     int sum = 0;
@@ -377,6 +378,15 @@ void orb_detect(const uint8_t *gray, int w, int h, int step, int nfeatures, doub
         ndesired *= factor;
     }
     per_level[nlevels - 1] = std::max(nfeatures - sum, 0);
+}
+
+void orb_detect(const uint8_t *gray, int w, int h, int step, int nfeatures, double scaleFactor, int nlevels,
+                int edgeThreshold, int patchSize, int fastThreshold, std::vector<KeyPt> &all) {
+    all.clear();
+    Pyramid P;
+    build_pyramid(gray, w, h, step, nlevels, scaleFactor, P);
+    std::vector<int> per_level;
+    level_budget(nfeatures, scaleFactor, nlevels, per_level);
     const int half = patchSize / 2;
     std::vector<int> umax;
     umax_table(half, umax);
@@ -507,18 +517,58 @@ int vso_fast9_16(const uint8_t *gray, int w, int h, int threshold, float *out_xy
     return 0;
 }
 
+// Read-only views of detect's intermediates (tests/ref_orb.py holds them to definitions).
+// The pyramid of orb_detect / orb_compute without its reflect frame: level l (sizes[2l], sizes[2l+1]) packed row after row.
+int vso_orb_pyramid(const uint8_t *gray, int w, int h, int nlevels, uint8_t *out, int64_t cap, int32_t *sizes) {
+    if (!gray || !out || !sizes || w < 1 || h < 1 || nlevels < 1) return -1;
+    Pyramid P;
+    build_pyramid(gray, w, h, w, nlevels, kScaleFactor, P);
+    int64_t off = 0;
+    for (int l = 0; l < nlevels; l++) {
+        sizes[2 * l] = P.lw[l];
+        sizes[2 * l + 1] = P.lh[l];
+        if (off + (int64_t)P.lw[l] * P.lh[l] > cap) return -2;
+        for (int y = 0; y < P.lh[l]; y++) std::memcpy(out + off + (int64_t)y * P.lw[l], P.level_ptr(l) + (size_t)y * P.bufw, P.lw[l]);
+        off += (int64_t)P.lw[l] * P.lh[l];
+    }
+    return 0;
+}
+
+int vso_orb_level_budget(int nfeatures, int nlevels, int32_t *out) {
+    if (!out || nlevels < 1) return -1;
+    std::vector<int> b;
+    level_budget(nfeatures, kScaleFactor, nlevels, b);
+    for (int l = 0; l < nlevels; l++) out[l] = b[l];
+    return 0;
+}
+
+// umax[0..half] of the intensity-centroid disc
+int vso_orb_umax(int half, int32_t *out) {
+    if (!out || half < 1) return -1;
+    std::vector<int> u;
+    umax_table(half, u);
+    for (int v = 0; v <= half; v++) out[v] = u[v];
+    return 0;
+}
+
+int vso_fast_atan2(const float *y, const float *x, int n, float *out) {
+    if (!y || !x || !out || n < 0) return -1;
+    for (int i = 0; i < n; i++) out[i] = fast_atan2(y[i], x[i]);
+    return 0;
+}
+
 int vso_resize_linear_exact(const uint8_t *src, int sw, int sh, uint8_t *dst, int dw, int dh) {
     if (!src || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1) return -1;
     resize_linear_exact(src, sw, sh, sw, dst, dw, dh, dw);
     return 0;
 }
 
-// ORB(nfeatures, 1.2, 8, 31, 0, 2, HARRIS, 31, fastThreshold)->detect(gray): 6 floats per keypoint
+// ORB(nfeatures, 1.2f, 8, 31, 0, 2, HARRIS, 31, fastThreshold)->detect(gray): 6 floats per keypoint
 // (x, y, size, angle, response, octave)
 int vso_orb_detect(const uint8_t *gray, int w, int h, int nfeatures, int fast_threshold, float *out_kp, int cap,
                    int32_t *out_n) {
     std::vector<KeyPt> k;
-    orb_detect(gray, w, h, w, nfeatures, 1.2, 8, 31, 31, fast_threshold, k);
+    orb_detect(gray, w, h, w, nfeatures, kScaleFactor, 8, 31, 31, fast_threshold, k);
     *out_n = (int32_t)k.size();
     for (int i = 0; i < (int)k.size() && i < cap; i++) {
         float *o = out_kp + 6 * i;
@@ -553,9 +603,9 @@ int vso_extract_features_grid(uint8_t *bgr, int w, int h, int stride, int nrows,
             // ORB::detect on the ROI: cvtColor(BGR2GRAY) of the cell
             bgr_to_gray(bgr + (size_t)sy * stride + 3 * sx, cw, ch, stride, cell_gray);
             std::vector<KeyPt> temp;
-            orb_detect(cell_gray.data(), cw, ch, cw, nfeatures, 1.2, 8, 31, 31, 20, temp);      // :33
+            orb_detect(cell_gray.data(), cw, ch, cw, nfeatures, kScaleFactor, 8, 31, 31, 20, temp);      // :33
             if ((int)temp.size() < nfeatures)                                                   // :34
-                orb_detect(cell_gray.data(), cw, ch, cw, nfeatures, 1.2, 8, 31, 31, 5, temp);   // :35
+                orb_detect(cell_gray.data(), cw, ch, cw, nfeatures, kScaleFactor, 8, 31, 31, 5, temp);   // :35
             for (KeyPt k : temp) {                                                              // :37-40
                 k.x = sx + k.x;
                 k.y = sy + k.y;
@@ -564,7 +614,7 @@ int vso_extract_features_grid(uint8_t *bgr, int w, int h, int stride, int nrows,
         }
     std::vector<uint8_t> gray, desc;
     bgr_to_gray(bgr, w, h, stride, gray);
-    orb_compute(gray.data(), w, h, w, keypoints, 1.2, pattern, desc);                           // :43
+    orb_compute(gray.data(), w, h, w, keypoints, kScaleFactor, pattern, desc);                           // :43
     *out_n = (int32_t)keypoints.size();
     for (int i = 0; i < (int)keypoints.size() && i < cap; i++) {                                // :47-49
         out_xy[2 * i] = keypoints[i].x;

@@ -5,7 +5,10 @@ overflows and its chunk-loop fall-back runs --, blocks on noise, checkerboards, 
 keypoint capacities below and above what is found.  Outlined image, keypoint count, coordinates and order, angles, octaves and
 descriptors must equal the oracle's.
 
-`python tests/fuzz_grid.py SEED SECONDS` runs it for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
+With ref_every = k, every k-th case is also held to the definitional reference tests/ref_orb.py (sets per cell and level,
+coordinates, angles, decided descriptor bits, count).
+
+`python tests/fuzz_grid.py SEED SECONDS [K]` runs it for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
 import sys
 import time
 
@@ -13,7 +16,14 @@ import numpy as np
 import torch
 
 
-def run(ctx, o, seed, cases=None, seconds=None):
+def check_ref(o, bgr, nrows, ncols, pat, xy, desc, ao, cap, n_found, stats=None):
+    """One frame's outputs (truncated to cap) against ref_orb."""
+    import ref_orb
+    ref = ref_orb.grid_reference(bgr, nrows, ncols, o)
+    return ref_orb.check_grid(ref, xy, desc, ao, o, pat, cap=cap if n_found > cap else None, stats=stats)
+
+
+def run(ctx, o, seed, cases=None, seconds=None, ref_every=0, stats=None):
     from vslam_amd import synth
     rng = np.random.default_rng(seed)
     pat = synth.brief_pattern()
@@ -68,6 +78,9 @@ def run(ctx, o, seed, cases=None, seconds=None):
             assert np.array_equal(out["xy"][f, :k].view(np.uint32), xy[:k].view(np.uint32)), ("xy",) + tag
             assert np.array_equal(out["angle_octave"][f, :k].view(np.uint32), ao[:k].view(np.uint32)), ("angle / octave",) + tag
             assert np.array_equal(out["desc"][f, :k], desc[:k]), ("descriptors",) + tag
+            if ref_every and done % ref_every == 0:
+                check_ref(o, bgr[f], nrows, ncols, pat, out["xy"][f, :k], out["desc"][f, :k], out["angle_octave"][f, :k],
+                          cap, len(xy), stats)
         done += 1
     return done
 
@@ -80,4 +93,5 @@ if __name__ == "__main__":
     from vslam_amd import Context
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     secs = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
-    print("fuzz ok:", run(Context(0), Oracle(), seed, seconds=secs), "cases")
+    every = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    print("fuzz ok:", run(Context(0), Oracle(), seed, seconds=secs, ref_every=every), "cases")

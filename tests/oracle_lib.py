@@ -208,6 +208,38 @@ class Oracle:
         assert self.lib.vso_orb_detect(_p(gray, C.c_uint8), w, h, nfeatures, fast_threshold, _p(out, C.c_float), cap, C.byref(n)) == 0
         return out[:n.value].copy()
 
+    def orb_pyramid(self, gray, nlevels=8):
+        """The detector's pyramid without its reflect frame: a list of nlevels u8 images."""
+        gray = np.ascontiguousarray(gray, dtype=np.uint8)
+        h, w = gray.shape
+        cap = 4 * w * h + 64
+        out = np.zeros(cap, dtype=np.uint8)
+        sizes = np.zeros(2 * nlevels, dtype=np.int32)
+        assert self.lib.vso_orb_pyramid(_p(gray, C.c_uint8), w, h, nlevels, _p(out, C.c_uint8), C.c_int64(cap),
+                                        _p(sizes, C.c_int32)) == 0
+        levels, off = [], 0
+        for l in range(nlevels):
+            lw, lh = int(sizes[2 * l]), int(sizes[2 * l + 1])
+            levels.append(out[off:off + lw * lh].reshape(lh, lw).copy())
+            off += lw * lh
+        return levels
+
+    def orb_level_budget(self, nfeatures=500, nlevels=8):
+        out = np.zeros(nlevels, dtype=np.int32)
+        assert self.lib.vso_orb_level_budget(nfeatures, nlevels, _p(out, C.c_int32)) == 0
+        return out
+
+    def orb_umax(self, half=15):
+        out = np.zeros(half + 1, dtype=np.int32)
+        assert self.lib.vso_orb_umax(half, _p(out, C.c_int32)) == 0
+        return out
+
+    def fast_atan2(self, y, x):
+        y = np.ascontiguousarray(y, dtype=np.float32); x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.zeros(len(y), dtype=np.float32)
+        assert self.lib.vso_fast_atan2(_p(y, C.c_float), _p(x, C.c_float), len(y), _p(out, C.c_float)) == 0
+        return out
+
     def extract_features_grid(self, bgr, nrows, ncols, pattern, cap=100000):
         """Returns (outlined bgr copy, xy, desc, angle_octave)."""
         b = np.ascontiguousarray(bgr, dtype=np.uint8).copy()

@@ -23,7 +23,11 @@ def test_ransac_kernels_on_random_and_degenerate_inputs(ctx, oracle):
 
 def test_grid_extractor_on_random_shapes_grids_and_content(ctx, oracle):
     import fuzz_grid
-    assert fuzz_grid.run(ctx, oracle, seed=20261008, cases=60) == 60
+    import ref_orb
+    stats = ref_orb.new_stats()
+    assert fuzz_grid.run(ctx, oracle, seed=20261008, cases=60, ref_every=1, stats=stats) == 60   # and to tests/ref_orb.py
+    assert stats["points"] > 2000 and stats["undecided_bits"] <= 0.01 * stats["bits"], stats
+    assert stats["undecided_cells"] == 0 and stats["undecided_levels"] == 0, stats
 
 
 def test_fuzz_assoc_slice(ctx, oracle):

@@ -1,37 +1,8 @@
 """CPU checks of the a4 oracle pieces (oracle/vso_orb.cpp) against independent definitions."""
 import numpy as np
 
+from orb_cases import fast_bruteforce
 from vslam_amd import synth
-
-CIRCLE = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3),
-          (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
-
-
-def fast_bruteforce(img, t):
-    """FAST-9/16 from its definition: 9 contiguous circle pixels all darker than v - t or all brighter
-    than v + t; score = largest t' for which that still holds; strict 3x3 non-max suppression."""
-    h, w = img.shape
-    g = img.astype(np.int32)
-    score = np.zeros((h, w), np.int32)
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            d = np.array([g[y, x] - g[y + dy, x + dx] for dx, dy in CIRCLE])
-            best = -10 ** 9
-            for s in range(16):
-                arc = d[[(s + j) % 16 for j in range(9)]]
-                best = max(best, arc.min(), (-arc).min())
-            if best > t:
-                score[y, x] = best - 1
-    out = []
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            s = score[y, x]
-            if s > 0:
-                nb = score[y - 1:y + 2, x - 1:x + 2].copy()
-                nb[1, 1] = -1
-                if (s > nb).all():
-                    out.append((x, y, s))
-    return np.array(out, np.float32).reshape(-1, 3)
 
 
 def test_fast_matches_definition(oracle):

@@ -2,7 +2,7 @@
 //
 // Replaces extract_features(Frame&, nrows, ncols), /root/reference/src/Frame.cpp:16-51 (the
 // extractor whose only call is commented out at src/vslam.cpp:63; it is the "ORB/FAST" of the
-// north star).  Per cell: black 1-px outline drawn into the image (:32), ORB(500, 1.2, 8, 31, 0, 2,
+// north star).  Per cell: black 1-px outline drawn into the image (:32), ORB(500, 1.2f, 8, 31, 0, 2,
 // HARRIS_SCORE, 31, fastThreshold 20)->detect, replaced by the fastThreshold-5 result when fewer
 // than 500 were found (:33-36); keypoints shifted to image coordinates (:37-40); then
 // ORB::compute over the whole (outlined) image (:43).
@@ -43,6 +43,8 @@ namespace {
 constexpr int kMaxLevels = 8;
 constexpr int kEdge = 31;         // edgeThreshold = patchSize
 constexpr int kNFeatures = 500;   // src/Frame.cpp:22-23
+// ORB::create takes scaleFactor as a float and src/Frame.cpp:23-24 passes 1.2f: level scales are (float)pow((double)1.2f, l)
+constexpr double kScaleFactor = (double)1.2f;
 constexpr int kFastMin = 5;       // lowest FAST threshold any detector here uses
 constexpr int kThr[2] = {20, 5};  // list t = 0: fastThreshold 20, t = 1: the fallback's 5
 
@@ -75,7 +77,7 @@ int make_geom(int w, int h, int nrows, int ncols, Geom &G) {
     G.nlv = 0;
     bool open = true;
     for (int l = 0; l < kMaxLevels; l++) {   // orb.cpp: Size(cvRound(w / scale), cvRound(h / scale)) with float scale
-        const float sc = (float)std::pow(1.2, (double)l);
+        const float sc = (float)std::pow(kScaleFactor, (double)l);
         G.scale[l] = sc;
         const float inv = 1.0f / sc;
         G.clw[l] = (int)std::lrint(G.cw * inv);
@@ -111,7 +113,7 @@ int make_geom(int w, int h, int nrows, int ncols, Geom &G) {
     G.fframe = (fo + 15) & ~15;
     G.ttotal = to;
     {   // computeKeyPoints' nfeaturesPerLevel (all 8 levels: the quotas do not depend on what a level can hold)
-        const float factor = (float)(1.0 / 1.2);
+        const float factor = (float)(1.0 / kScaleFactor);
         float ndesired = kNFeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)kMaxLevels));
         int sum = 0;
         for (int l = 0; l < kMaxLevels - 1; l++) {
