@@ -250,25 +250,42 @@ def test_null_pattern_means_orbs_learned_table(ctx, oracle):
 
 def test_frontend_pairs_end_to_end(ctx, oracle):
     """The whole path bench.py times, on C1-like inputs (640x480, 500 keypoints, 512 hypotheses):
-    extract both frames, match, RANSAC; inlier matches and F must equal the oracle's."""
+    extract both frames, match, RANSAC; inlier matches and F must equal the oracle's.  Then the seed buffer is
+    rewritten in place and match_features is called on it with the same batch and hypotheses: its sets come from
+    the new seeds, not from the generator outputs frontend_pairs produced ahead of time."""
     w, h, maxc, Hy, thr, P = 640, 480, 500, 512, 10.0, 2
     bgr = synth.frames_numpy(0x5EED0000, P, w, h)
     pat = synth.brief_pattern()
     ca, sa = synth.keypoint_rotation()
     seeds = np.array([0x5EED0000 ^ p for p in range(P)], np.uint32)
-    out = ctx.frontend_pairs(torch.from_numpy(bgr).cuda(), P, maxc, ca, sa, torch.from_numpy(pat).cuda(),
-                             torch.from_numpy(seeds.view(np.int32)).cuda(), Hy, thr)
+    d_seeds = torch.from_numpy(seeds.view(np.int32)).cuda()
+    d_out = ctx.frontend_pairs(torch.from_numpy(bgr).cuda(), P, maxc, ca, sa, torch.from_numpy(pat).cuda(), d_seeds, Hy, thr)
     ctx.synchronize()
-    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out = {k: v.cpu().numpy() for k, v in d_out.items()}
+    feats = []
     for p in range(P):
         a = oracle.extract_features(bgr[p], maxc, ca, sa, pat)
         b = oracle.extract_features(bgr[P + p], maxc, ca, sa, pat)
+        feats.append((a, b))
         ref = oracle.match_features(a["xy"], a["desc"], b["xy"], b["desc"], int(seeds[p]), Hy, thr)
         assert ref["rc"] == 0 and ref["prelim"] > 100, "synthetic pair should match"
         k = len(ref["matches"])
         assert out["best"][p, 3] == k and k > 30, p
         assert np.array_equal(out["matches"][p, :k], ref["matches"]), p
         assert np.array_equal(out["F"][p].view(np.uint32), ref["F"].view(np.uint32)), p
+
+    new_seeds = seeds ^ np.uint32(0xA5A5A5A5)
+    d_seeds.copy_(torch.from_numpy(new_seeds.view(np.int32)))
+    xy, desc, n = d_out["xy"], d_out["desc"], d_out["n"]
+    m = ctx.match_features(xy[:P], desc[:P], n[:P], xy[P:], desc[P:], n[P:], d_seeds, Hy, thr)
+    ctx.synchronize()
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    for p, (a, b) in enumerate(feats):
+        ref = oracle.match_features(a["xy"], a["desc"], b["xy"], b["desc"], int(new_seeds[p]), Hy, thr)
+        assert not np.array_equal(ref["F"].view(np.uint32), out["F"][p].view(np.uint32)), p   # the new seeds draw other sets
+        k = len(ref["matches"])
+        assert m["best"][p, 3] == k and np.array_equal(m["matches"][p, :k], ref["matches"]), p
+        assert np.array_equal(m["F"][p].view(np.uint32), ref["F"].view(np.uint32)), p
 
 
 def test_good_features_tiny_max_corners_forces_slow_path(ctx, oracle):

@@ -132,6 +132,43 @@ def test_extract_from_bgr_on_seams(ctx, oracle, w, h, pad):
         assert np.array_equal(out["nodes"][f, :k], r["nodes"]), (w, h, pad, f)
 
 
+def test_stage_entries_after_a_padded_extract(ctx, oracle):
+    """extract_features at a width that gets padded internal rows (67), then the stage entry points on the same context with
+    the caller's packed rows, at that width and at a multiple of 4: each stage reads rows of exactly `width` bytes."""
+    h, maxc = 96, 150
+    pat = synth.brief_pattern()
+    ca, sa = synth.keypoint_rotation()
+    bgr = synth.frames_numpy(4100, 1, 67, h)
+    out = ctx.extract_features(torch.from_numpy(bgr).cuda(), maxc, ca, sa, torch.from_numpy(pat).cuda())
+    ctx.synchronize()
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    for f in range(bgr.shape[0]):
+        r = oracle.extract_features(bgr[f], maxc, ca, sa, pat)
+        assert out["n"][f] == r["n"] and np.array_equal(out["desc"][f, :r["n"]], r["desc"]), f
+    rng = np.random.default_rng(4101)
+    for w in (67, 68):
+        gray = textured(w, h, 4102 + w)
+        t = torch.from_numpy(gray).cuda()
+        eig = ctx.min_eigen(t)
+        blur = ctx.gaussian7(t)
+        xy, n = ctx.good_features(t, maxc)
+        K = 60   # keypoints on both sides of the 31-pixel border
+        pts = np.rint(np.stack([rng.uniform(20, w - 21, (2, K)), rng.uniform(20, h - 21, (2, K))], -1)).astype(np.float32)
+        pts[:, :2] = [[31, 31], [w - 32, h - 32]]
+        xy_out, desc, n_out = ctx.orb_describe(blur, torch.from_numpy(pts).cuda(), torch.full((2,), K, dtype=torch.int32).cuda(),
+                                               ca, sa, torch.from_numpy(pat).cuda())
+        ctx.synchronize()
+        eig, blur, xy, n = eig.cpu().numpy(), blur.cpu().numpy(), xy.cpu().numpy(), n.cpu().numpy()
+        desc, n_out = desc.cpu().numpy(), n_out.cpu().numpy()
+        for f in range(2):
+            assert np.array_equal(eig[f].view(np.uint32), oracle.min_eigen(gray[f]).view(np.uint32)), (w, f)
+            assert np.array_equal(blur[f], oracle.gaussian7(gray[f])), (w, f)
+            ref = oracle.good_features(gray[f], maxc)
+            assert n[f] == len(ref) and np.array_equal(xy[f, :n[f]], ref), (w, f)
+            rd, keep = oracle.orb_describe(blur[f], pts[f], ca, sa, pat)
+            assert 0 < len(keep) < K and n_out[f] == len(keep) and np.array_equal(desc[f, :len(keep)], rd), (w, f)
+
+
 @pytest.mark.parametrize("w,h", [(509, 77), (510, 77), (511, 77), (1277, 96), (257, 64), (258, 70), (259, 64), (512, 77)])
 def test_detected_corners_before_the_border_filter(ctx_exp, oracle, w, h):
     """The corners goodFeaturesToTrack returns, in rank order, BEFORE ORB::compute drops the ones within 31 pixels of the border

@@ -1,4 +1,4 @@
-"""The invariant behind the device's padded rows (vslam_ctx::img_pitch, HISTORY.md round 6): an image whose rows are continued
+"""The invariant behind the device's padded rows (the launchers' `pitch` argument, HISTORY.md round 6): an image whose rows are continued
 by their BORDER_REFLECT_101 mirror, filtered as a wider image, carries the original image's result in its first `w` columns.
 Checked on the oracle alone (no GPU): the 7 x 7 Gaussian for every pad the device can choose, and the corner response, where
 the one column next to the pad differs (a mirrored x-derivative has the opposite sign: the device negates that column's xy

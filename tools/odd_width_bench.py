@@ -1,4 +1,4 @@
-"""The front-end step at a width that is no multiple of 4 (padded internal rows, vslam_ctx::img_pitch) beside the same frames cut to
+"""The front-end step at a width that is no multiple of 4 (padded internal rows: the launchers' `pitch` argument) beside the same frames cut to
 a multiple of 4: ms per batch and per-stage event times -- the same kernels run in both (tools/_odd_width_prof.sh puts rocprofv3
 on it).   python tools/odd_width_bench.py [--pairs 64] [--w 1278] [--h 720]"""
 import argparse

@@ -1,6 +1,6 @@
 // cv::GaussianBlur 7x7, sigma 2, 8-bit fixed point, as ORB::compute applies it before sampling (reference:
 // src/Frame.cpp:68) for gfx950: gaussian7_stream_kernel (rows of a multiple of 4 bytes: width % 4 == 0, or padded rows with a
-// mirrored tail, vslam_ctx::img_pitch) and gaussian7_kernel (any width).
+// mirrored tail, see vs_launch_gaussian7) and gaussian7_kernel (any width).
 #include "image_common.h"
 
 namespace {
@@ -185,15 +185,15 @@ __global__ __launch_bounds__(256) void gaussian7_stream_kernel(const uint8_t *__
 
 }  // namespace
 
-int vs_launch_gaussian7(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, uint8_t *out) {
+int vs_launch_gaussian7(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, uint8_t *out) {
     VS_REQUIRE(ctx, gray && out, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, frames > 0 && w >= 4 && h >= 4, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, frames > 0 && w >= 4 && h >= 4 && pitch >= w, VSLAM_ERR_INVALID);
     VsProfScope ps(ctx, "gaussian7_kernel");
-    if (vs_pitch(ctx, w) != w) {
-        // Padded rows (vslam_ctx::img_pitch): at least three mirrored columns follow column w - 1, which is all a 7-tap row
-        // filter with BORDER_REFLECT_101 reads past it, so the padded plane filtered as an image of `pitch` columns holds the
+    if (pitch != w) {
+        // Padded rows (`pitch` > w): at least three mirrored columns follow column w - 1, which is all a 7-tap row filter
+        // with BORDER_REFLECT_101 reads past it, so the padded plane filtered as an image of `pitch` columns holds the
         // image's result in its first w columns (its own mirroring happens at column pitch - 1, three or more columns away).
-        w = vs_pitch(ctx, w);
+        w = pitch;
         VS_REQUIRE(ctx, w % 4 == 0, VSLAM_ERR_INVALID);
     }
     if (w % 4 == 0 && ((reinterpret_cast<uintptr_t>(gray) | reinterpret_cast<uintptr_t>(out)) & 3) == 0) {

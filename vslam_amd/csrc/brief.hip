@@ -396,32 +396,34 @@ __global__ __launch_bounds__(kKT) void rbrief_tile_kernel(const uint8_t *__restr
 }  // namespace
 
 // The rotated pattern table depends on the pattern and the angle alone: a caller that has an idle stream ahead of the
-// description stage (vslam_extract_features: the auxiliary stream, in front of the blur) launches it there and
-// vs_launch_orb_describe skips its own launch.  The caller guarantees the ordering (it joins that stream before describing).
-int vs_launch_rbrief_rotate(vslam_ctx *ctx, const int8_t *pattern, float ca, float sa) {
-    int32_t *table = nullptr;
-    int rc = vs_arena_get(ctx, "rbrief.table", sizeof(int32_t) * 513, (void **)&table);
+// description stage (vslam_extract_features: the auxiliary stream, in front of the blur) launches it there and hands *table
+// to vs_launch_orb_describe, which then skips its own launch.  The caller guarantees the ordering (it joins that stream
+// before describing).
+int vs_launch_rbrief_rotate(vslam_ctx *ctx, const int8_t *pattern, float ca, float sa, const int32_t **table) {
+    int32_t *t = nullptr;
+    int rc = vs_arena_get(ctx, "rbrief.table", sizeof(int32_t) * 513, (void **)&t);
     if (rc) return rc;
-    rbrief_rotate_kernel<<<1, 512, 0, ctx->stream>>>(pattern, ca, sa, table);
+    rbrief_rotate_kernel<<<1, 512, 0, ctx->stream>>>(pattern, ca, sa, t);
     VS_HIP(ctx, hipGetLastError());
-    ctx->rbrief_table_ready = true;
+    *table = t;
     return VSLAM_OK;
 }
 
-int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, int w, int h,
+int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, int w, int h, int pitch,
                            const float *xy_in, const int32_t *n_in, int kp_stride, float ca, float sa,
-                           const int8_t *pattern, float *xy_out, uint8_t *desc, int32_t *n_out) {
+                           const int8_t *pattern, const int32_t *rotated_table, float *xy_out, uint8_t *desc,
+                           int32_t *n_out) {
     VS_REQUIRE(ctx, blurred && xy_in && n_in && pattern && xy_out && desc && n_out, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, frames > 0 && kp_stride > 0, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, frames > 0 && kp_stride > 0 && pitch >= w, VSLAM_ERR_INVALID);
     // the tile-staged descriptor kernel (VSLAM_RBRIEF_PATCH=1 selects round 2's per-keypoint staging, for A/B timing)
     static const bool patch_form = VS_EXPERIMENT_ENV("VSLAM_RBRIEF_PATCH") != nullptr;
     int tw = kTW, th = kTH;
     if (const char *e = VS_EXPERIMENT_ENV("VSLAM_RBRIEF_TILE")) sscanf(e, "%dx%d", &tw, &th);   // A/B timing
-    // Rows of the blurred plane may be longer than the image is wide (vslam_ctx::img_pitch: a mirrored tail nobody samples,
-    // keypoints keep 31 pixels from the image's border).  The kernels address and tile the plane by its rows, `wl`; only the
-    // border rule below sees the image's width.
+    // Rows of the blurred plane may be longer than the image is wide (`pitch` > w: a mirrored tail nobody samples, keypoints
+    // keep 31 pixels from the image's border).  The kernels address and tile the plane by its rows; only the border rule
+    // below sees the image's width.
     const int w_img = w;
-    w = vs_pitch(ctx, w);
+    w = pitch;
     while (vs_div_up(w, tw) * vs_div_up(h, th) > kTilesMax) {
         tw *= 2;
         th *= 2;
@@ -446,10 +448,9 @@ int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, i
         VsProfScope ps(ctx, "rbrief_kernel");
         const int per_frame = vs_div_up(kp_stride, kKT / 32);
         if (w % 4 == 0 && (reinterpret_cast<uintptr_t>(blurred) & 3) == 0) {
-            int32_t *table = nullptr;
-            int rc = vs_arena_get(ctx, "rbrief.table", sizeof(int32_t) * 513, (void **)&table);
-            if (rc) return rc;
-            if (!ctx->rbrief_table_ready) rbrief_rotate_kernel<<<1, 512, 0, ctx->stream>>>(pattern, ca, sa, table);
+            const int32_t *table = rotated_table;
+            if (!table)
+                if (int rc = vs_launch_rbrief_rotate(ctx, pattern, ca, sa, &table)) return rc;
             if (tiled) {
                 rbrief_tile_kernel<<<vs_xcd_grid(frames, ntiles), kKT, tile_lds, ctx->stream>>>(
                     blurred, w, h, kp_stride, table, tile_start, tile_kp, desc, frames, tw, th, tiles_x, ntiles);
@@ -463,7 +464,6 @@ int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, i
                                                                                     sa, pattern, desc, frames, per_frame);
         }
     }
-    ctx->rbrief_table_ready = false;   // a caller's early launch (vs_launch_rbrief_rotate) covers one describe call
     VS_HIP(ctx, hipGetLastError());
     return VSLAM_OK;
 }

@@ -42,10 +42,11 @@ int vs_aux_job_point(vslam_ctx *ctx, int point) {
     ctx->aux_job_at = 0;
     VS_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     VS_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->aux_stream;
-    const int rc = ctx->aux_job();
-    ctx->stream = main_stream;
+    int rc;
+    {
+        VsStreamScope on_aux(ctx, ctx->aux_stream);
+        rc = ctx->aux_job();
+    }
     ctx->aux_job = nullptr;
     if (rc) return rc;
     VS_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
@@ -611,64 +612,52 @@ int vslam_kdtree_cell_table(vslam_ctx *ctx, const int32_t *d_nodes, const float 
     return vs_launch_kdtree_cell_table(ctx, d_nodes, d_xy, d_n, batch, kp_stride, slots, d_table, d_ok);
 }
 
-// State that one entry point arms for a later stage of the same call (the rotated rBRIEF table queued ahead of the
-// description stage; the raw generator outputs queued ahead of vslam_match_features) must not outlive that call: on
-// an error return in between, the next call would otherwise skip work it needs.  Cleared on every exit.
-struct VsTableGuard {
-    vslam_ctx *c;
-    ~VsTableGuard() { c->rbrief_table_ready = false; c->fork_after_eigen = false; c->img_pitch = 0; }
-};
-struct VsPrefetchGuard {
-    vslam_ctx *c;
-    ~VsPrefetchGuard() { c->raw_seeds = nullptr; }
-};
-// rows for a width the dword kernels do not take as it is (vslam_ctx::img_pitch); 0: the width is fine (or too small to mirror)
-static inline int vs_padded_pitch(int width) { return (width % 4 != 0 && width >= 64) ? (width + 3 + 15) & ~15 : 0; }
+// Bytes per row of the internal gray / blurred planes for an image `width` bytes wide: a width the dword kernels do not take
+// as it is gets rows of a multiple of 16 bytes, at least 3 longer, whose tail holds the row's mirror (see
+// vslam_extract_features); any other width (a multiple of 4, or too small to mirror) keeps packed rows.
+static inline int vs_padded_pitch(int width) { return (width % 4 != 0 && width >= 64) ? (width + 3 + 15) & ~15 : width; }
 
 int vslam_bgr2gray(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int width, int height,
                    int row_stride, uint8_t *d_gray) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    return vs_launch_bgr2gray(ctx, d_bgr, frames, width, height, row_stride, d_gray);
+    return vs_launch_bgr2gray(ctx, d_bgr, frames, width, height, row_stride, d_gray, width);
 }
 
 int vslam_min_eigen(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int width, int height,
                     float *d_eig) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    return vs_launch_min_eigen(ctx, d_gray, frames, width, height, d_eig, nullptr);
+    return vs_launch_min_eigen(ctx, d_gray, frames, width, height, width, d_eig, nullptr);
 }
 
 int vslam_good_features(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int width, int height,
                         int max_corners, double quality, double min_distance, int kp_stride,
                         float *d_xy, int32_t *d_n) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    if (d_gray && vs_padded_pitch(width) && frames > 0 && height > 0) {   // see vslam_extract_features: the caller's rows, copied into padded ones
-        VsTableGuard guard{ctx};
-        const int pitch = vs_padded_pitch(width);
+    const int pitch = vs_padded_pitch(width);
+    if (d_gray && pitch != width && frames > 0 && height > 0) {   // see vslam_extract_features: the caller's rows, copied into padded ones
         uint8_t *padded = nullptr;
         if (int rc = vs_arena_get(ctx, "stage.gray_padded", (size_t)frames * pitch * height, (void **)&padded)) return rc;
         if (int rc = vs_launch_gray_pad(ctx, d_gray, frames, width, height, padded, pitch)) return rc;
-        ctx->img_pitch = pitch;
-        return vs_launch_good_features(ctx, padded, frames, width, height, max_corners, quality, min_distance, kp_stride, d_xy, d_n);
+        return vs_launch_good_features(ctx, padded, frames, width, height, pitch, max_corners, quality, min_distance, kp_stride,
+                                       d_xy, d_n);
     }
-    return vs_launch_good_features(ctx, d_gray, frames, width, height, max_corners, quality,
+    return vs_launch_good_features(ctx, d_gray, frames, width, height, width, max_corners, quality,
                                    min_distance, kp_stride, d_xy, d_n);
 }
 
 int vslam_gaussian7(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int width, int height,
                     uint8_t *d_out) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    if (d_gray && d_out && vs_padded_pitch(width) && frames > 0 && height >= 4) {
-        VsTableGuard guard{ctx};
-        const int pitch = vs_padded_pitch(width);
+    const int pitch = vs_padded_pitch(width);
+    if (d_gray && d_out && pitch != width && frames > 0 && height >= 4) {
         uint8_t *padded = nullptr, *blurred = nullptr;
         if (int rc = vs_arena_get(ctx, "stage.gray_padded", (size_t)frames * pitch * height, (void **)&padded)) return rc;
         if (int rc = vs_arena_get(ctx, "stage.blur_padded", (size_t)frames * pitch * height, (void **)&blurred)) return rc;
         if (int rc = vs_launch_gray_pad(ctx, d_gray, frames, width, height, padded, pitch)) return rc;
-        ctx->img_pitch = pitch;
-        if (int rc = vs_launch_gaussian7(ctx, padded, frames, width, height, blurred)) return rc;
+        if (int rc = vs_launch_gaussian7(ctx, padded, frames, width, height, pitch, blurred)) return rc;
         return vs_launch_gray_unpad(ctx, blurred, frames, width, height, pitch, d_out);
     }
-    return vs_launch_gaussian7(ctx, d_gray, frames, width, height, d_out);
+    return vs_launch_gaussian7(ctx, d_gray, frames, width, height, width, d_out);
 }
 
 int vslam_orb_describe(vslam_ctx *ctx, const uint8_t *d_blurred, int frames, int width, int height,
@@ -678,8 +667,8 @@ int vslam_orb_describe(vslam_ctx *ctx, const uint8_t *d_blurred, int frames, int
     if (!ctx) return VSLAM_ERR_INVALID;
     if (!d_pattern)
         if (int rc = vs_default_pattern(ctx, &d_pattern)) return rc;
-    return vs_launch_orb_describe(ctx, d_blurred, frames, width, height, d_xy_in, d_n_in, kp_stride,
-                                  cos_a, sin_a, d_pattern, d_xy_out, d_desc, d_n_out);
+    return vs_launch_orb_describe(ctx, d_blurred, frames, width, height, width, d_xy_in, d_n_in, kp_stride,
+                                  cos_a, sin_a, d_pattern, nullptr, d_xy_out, d_desc, d_n_out);
 }
 
 #ifdef VSLAM_EXPERIMENTS
@@ -688,12 +677,11 @@ int vslam_orb_describe(vslam_ctx *ctx, const uint8_t *d_blurred, int frames, int
 int vslam_debug_detect(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int width, int height, int row_stride, int max_corners,
                        int kp_stride, float *d_xy, int32_t *d_n) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    VsTableGuard table_guard{ctx};
-    ctx->img_pitch = vs_padded_pitch(width);
+    const int pitch = vs_padded_pitch(width);
     uint8_t *gray = nullptr;
-    if (int rc = vs_arena_get(ctx, "extract.gray", (size_t)frames * vs_pitch(ctx, width) * height, (void **)&gray)) return rc;
+    if (int rc = vs_arena_get(ctx, "extract.gray", (size_t)frames * pitch * height, (void **)&gray)) return rc;
     const VsBgrSource src{d_bgr, row_stride};
-    return vs_launch_good_features(ctx, gray, frames, width, height, max_corners, 0.01, 3.0, kp_stride, d_xy, d_n, &src);
+    return vs_launch_good_features(ctx, gray, frames, width, height, pitch, max_corners, 0.01, 3.0, kp_stride, d_xy, d_n, &src);
 }
 #endif
 
@@ -703,7 +691,6 @@ int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int
                            float *d_xy, uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n,
                            int32_t *d_n_detected) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    VsTableGuard table_guard{ctx};
     VS_REQUIRE(ctx, d_bgr && params && d_xy && d_desc && d_n, VSLAM_ERR_INVALID);
     vslam_extract_params with_table;
     if (!params->d_pattern) {   // the default: ORB's learned table
@@ -717,8 +704,8 @@ int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int
     // than the image is wide, the tail holding the row's BORDER_REFLECT_101 continuation (written by cvtColor): the same
     // kernels run on those rows and what they produce below column `width` is what the image alone would give
     // (blur.hip, response.hip: the one place that needs a correction is the sign of a mirrored x-derivative).
-    ctx->img_pitch = vs_padded_pitch(width);
-    const size_t px = (size_t)frames * vs_pitch(ctx, width) * height;
+    const int pitch = vs_padded_pitch(width);
+    const size_t px = (size_t)frames * pitch * height;
     uint8_t *gray = nullptr, *blur = nullptr;
     float *xy_det = nullptr;
     int32_t *n_det = nullptr;
@@ -734,33 +721,28 @@ int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int
     // selection stage is latency-bound and leaves most of the chip idle (not while per-kernel timing is on).
     const bool overlap = ctx->overlap_blur > 0 && !ctx->prof;
     const VsBgrSource src{d_bgr, row_stride};
-    ctx->fork_after_eigen = overlap;
-    rc = vs_launch_good_features(ctx, gray, frames, width, height, params->max_corners,                  // :56, :61
-                                 params->quality, params->min_distance, kp_stride, xy_det, n_det, &src);
-    ctx->fork_after_eigen = false;
-    if (rc) return rc;
+    if ((rc = vs_launch_good_features(ctx, gray, frames, width, height, pitch, params->max_corners,       // :56, :61
+                                      params->quality, params->min_distance, kp_stride, xy_det, n_det, &src, overlap)))
+        return rc;
+    const int32_t *table = nullptr;   // the rotated rBRIEF table when it is queued ahead of the description stage
     {
-        hipStream_t main_stream = ctx->stream;
-        if (overlap) ctx->stream = ctx->aux_stream;
+        VsStreamScope blur_stream(ctx, overlap ? ctx->aux_stream : ctx->stream);
         // The table the description stage will want: off the main stream's critical path.  It sits in FRONT of the blur on
         // purpose.  The 8-wave kernel finds every CU held by the selection's 1024-thread workgroups and waits about 65 us
         // for a slot (profiles/r04_step_timeline.txt), which is what lets the selection take its places before the blur's
         // waves arrive: queued at the head of the auxiliary stream instead (round 5, tools/ab_lib.py, same process,
         // alternating) the blur starts at the fork and the step is unchanged with one batch in flight (2.950 vs 2.950 ms) and
         // SLOWER with three (2.764 -> 2.800 ms on the hard data, 2.604 -> 2.664 on the easy data).
-        if (overlap && vs_pitch(ctx, width) % 4 == 0)
-            rc = vs_launch_rbrief_rotate(ctx, params->d_pattern, params->cos_a, params->sin_a);
-        if (rc == VSLAM_OK)
-            rc = vs_launch_gaussian7(ctx, gray, frames, width, height, blur);                            // ORB::compute
-        ctx->stream = main_stream;
-        if (rc) return rc;
-        if (overlap) {
-            VS_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
-            VS_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        }
+        if (overlap && pitch % 4 == 0)
+            if ((rc = vs_launch_rbrief_rotate(ctx, params->d_pattern, params->cos_a, params->sin_a, &table))) return rc;
+        if ((rc = vs_launch_gaussian7(ctx, gray, frames, width, height, pitch, blur))) return rc;        // ORB::compute
     }
-    if ((rc = vs_launch_orb_describe(ctx, blur, frames, width, height, xy_det, n_det, kp_stride,         // :68-72
-                                     params->cos_a, params->sin_a, params->d_pattern, d_xy, d_desc, d_n)))
+    if (overlap) {
+        VS_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux_stream));
+        VS_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    }
+    if ((rc = vs_launch_orb_describe(ctx, blur, frames, width, height, pitch, xy_det, n_det, kp_stride,  // :68-72
+                                     params->cos_a, params->sin_a, params->d_pattern, table, d_xy, d_desc, d_n)))
         return rc;
     if (d_nodes)
         if ((rc = vs_launch_kdtree_build(ctx, d_xy, d_n, frames, kp_stride, d_nodes))) return rc;       // :76
@@ -822,13 +804,11 @@ int vslam_associate_map_points(vslam_ctx *ctx, const float *d_map_points, const 
                                d_claim);
 }
 
-// match_features, src/Frame.cpp:82-105
-int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_desc1,
-                         const int32_t *d_n1, const float *d_xy2, const uint8_t *d_desc2,
-                         const int32_t *d_n2, int batch, int kp_stride, const uint32_t *d_seeds,
-                         int hyp, float threshold, int32_t *d_matches, int32_t *d_best, float *d_F,
-                         int32_t *d_prelim_m) {
-    if (!ctx) return VSLAM_ERR_INVALID;
+// match_features, src/Frame.cpp:82-105.  raw_ready: vs_sets_prefetch has queued the raw generator outputs of exactly these
+// (seeds, batch, hyp) (ev_raw marks them), so only the mapping is left.
+static int vs_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_desc1, const int32_t *d_n1, const float *d_xy2,
+                             const uint8_t *d_desc2, const int32_t *d_n2, int batch, int kp_stride, const uint32_t *d_seeds, int hyp,
+                             float threshold, int32_t *d_matches, int32_t *d_best, float *d_F, int32_t *d_prelim_m, bool raw_ready) {
     VS_REQUIRE(ctx, d_xy1 && d_desc1 && d_n1 && d_xy2 && d_desc2 && d_n2 && d_seeds, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_matches && d_best && d_F, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, batch > 0 && kp_stride > 0 && hyp > 0, VSLAM_ERR_INVALID);
@@ -850,11 +830,9 @@ int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_de
 
     if ((rc = vs_launch_match(ctx, d_desc1, d_n1, d_desc2, d_n2, batch, kp_stride, pairs, m, nullptr))) return rc;
     if ((rc = vs_aux_job_point(ctx, 1))) return rc;
-    if (ctx->raw_seeds == d_seeds && ctx->raw_batch == batch && ctx->raw_hyp == hyp) {
-        // the raw generator outputs were produced ahead of time (vs_sets_prefetch): only the mapping is left
+    if (raw_ready) {
         uint32_t *raw = nullptr;
         if ((rc = vs_arena_get(ctx, "mf.raw", sizeof(uint32_t) * vs_ransac_raw_words(hyp) * (size_t)batch, (void **)&raw))) return rc;
-        ctx->raw_seeds = nullptr;
         VS_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_raw, 0));
         if ((rc = vs_launch_ransac_map(ctx, m, batch, hyp, raw, sets, draws))) return rc;
     } else if ((rc = vs_launch_ransac_sets(ctx, d_seeds, m, batch, hyp, sets, draws))) {
@@ -865,28 +843,33 @@ int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_de
                             d_best, d_matches, hypF, hyp_count, hyp_sum);
 }
 
+int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_desc1,
+                         const int32_t *d_n1, const float *d_xy2, const uint8_t *d_desc2,
+                         const int32_t *d_n2, int batch, int kp_stride, const uint32_t *d_seeds,
+                         int hyp, float threshold, int32_t *d_matches, int32_t *d_best, float *d_F,
+                         int32_t *d_prelim_m) {
+    if (!ctx) return VSLAM_ERR_INVALID;
+    return vs_match_features(ctx, d_xy1, d_desc1, d_n1, d_xy2, d_desc2, d_n2, batch, kp_stride, d_seeds, hyp, threshold, d_matches,
+                             d_best, d_F, d_prelim_m, false);
+}
+
 // The mt19937 outputs RANSAC will draw its sets from depend on the seeds alone: generate them on the auxiliary stream
-// while the frames are being extracted.  vslam_match_features picks them up when called with the same (seeds, batch, hyp).
-static int vs_sets_prefetch(vslam_ctx *ctx, const uint32_t *d_seeds, int batch, int hyp) {
-    ctx->raw_seeds = nullptr;
+// while the frames are being extracted.  *queued says whether it did; vs_match_features then takes them up.
+static int vs_sets_prefetch(vslam_ctx *ctx, const uint32_t *d_seeds, int batch, int hyp, bool *queued) {
+    *queued = false;
     if (!d_seeds || batch <= 0 || hyp <= 0) return VSLAM_OK;   // the entry point proper reports bad arguments
     if (!ctx->sets_prefetch) return VSLAM_OK;                  // the generator then runs in line, in front of the mapping
     uint32_t *raw = nullptr;
     int rc = vs_arena_get(ctx, "mf.raw", sizeof(uint32_t) * vs_ransac_raw_words(hyp) * (size_t)batch, (void **)&raw);
     if (rc) return rc;
-    hipStream_t main_stream = ctx->stream;
     if (!ctx->prof) {   // everything queued so far (the previous step's mapping kernel reads `raw`) comes first
         VS_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         VS_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-        ctx->stream = ctx->aux_stream;
     }
-    rc = vs_launch_ransac_mt(ctx, d_seeds, batch, hyp, raw);
-    ctx->stream = main_stream;
-    if (rc) return rc;
-    VS_HIP(ctx, hipEventRecord(ctx->ev_raw, ctx->prof ? ctx->stream : ctx->aux_stream));
-    ctx->raw_seeds = d_seeds;
-    ctx->raw_batch = batch;
-    ctx->raw_hyp = hyp;
+    VsStreamScope gen_stream(ctx, ctx->prof ? ctx->stream : ctx->aux_stream);
+    if ((rc = vs_launch_ransac_mt(ctx, d_seeds, batch, hyp, raw))) return rc;
+    VS_HIP(ctx, hipEventRecord(ctx->ev_raw, ctx->stream));
+    *queued = true;
     return VSLAM_OK;
 }
 
@@ -897,13 +880,13 @@ int vslam_frontend_pairs(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, int wi
                          uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches,
                          int32_t *d_best, float *d_F) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    VsPrefetchGuard prefetch_guard{ctx};
     VS_REQUIRE(ctx, pairs > 0, VSLAM_ERR_INVALID);
     // The k-d trees are an output of the path but not an input of match/RANSAC: build them on the
     // auxiliary stream beside the matching stages (fork after extraction, join at the end).  With
     // per-kernel timing on, everything stays on one stream so the event brackets are clean.
     const bool overlap = d_nodes && !ctx->prof && ctx->tree_fork != 5;   // 5: in line on the main stream, at the end of extraction
-    int rc = vs_sets_prefetch(ctx, d_seeds, pairs, hyp);
+    bool raw_ready;
+    int rc = vs_sets_prefetch(ctx, d_seeds, pairs, hyp, &raw_ready);
     if (rc) return rc;
     rc = vslam_extract_features(ctx, d_bgr, 2 * pairs, width, height, row_stride, params, kp_stride,
                                     d_xy, d_desc, overlap ? nullptr : d_nodes, d_n, nullptr);
@@ -912,9 +895,9 @@ int vslam_frontend_pairs(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, int wi
     if (overlap)
         if ((rc = vs_defer_tree_build(ctx, d_xy, d_n, 2 * pairs, kp_stride, d_nodes))) return rc;
     const size_t half = (size_t)pairs * kp_stride;
-    rc = vslam_match_features(ctx, d_xy, d_desc, d_n, d_xy + 2 * half, d_desc + VSLAM_DESC_BYTES * half,
-                              d_n + pairs, pairs, kp_stride, d_seeds, hyp, threshold, d_matches, d_best,
-                              d_F, nullptr);
+    rc = vs_match_features(ctx, d_xy, d_desc, d_n, d_xy + 2 * half, d_desc + VSLAM_DESC_BYTES * half,
+                           d_n + pairs, pairs, kp_stride, d_seeds, hyp, threshold, d_matches, d_best,
+                           d_F, nullptr, raw_ready);
     // a fork point the matching stages never passed (point 4 lies in the branch VSLAM_OPT_RANSAC_ALL_SUMS does not take): the
     // build still has to run, or the join below waits on an event of an earlier call and d_nodes stays unwritten
     if (rc == VSLAM_OK && overlap && ctx->aux_job) rc = vs_aux_job_point(ctx, ctx->aux_job_at);
@@ -986,10 +969,10 @@ int vslam_frontend_sequence(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, in
                             uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches,
                             int32_t *d_best, float *d_F) {
     if (!ctx) return VSLAM_ERR_INVALID;
-    VsPrefetchGuard prefetch_guard{ctx};
     VS_REQUIRE(ctx, frames >= 2, VSLAM_ERR_INVALID);
     const bool overlap = d_nodes && !ctx->prof && ctx->tree_fork != 5;   // k-d trees beside the matching stages, as in vslam_frontend_pairs
-    int rc = vs_sets_prefetch(ctx, d_seeds, frames - 1, hyp);
+    bool raw_ready;
+    int rc = vs_sets_prefetch(ctx, d_seeds, frames - 1, hyp, &raw_ready);
     if (rc) return rc;
     rc = vslam_extract_features(ctx, d_bgr, frames, width, height, row_stride, params, kp_stride, d_xy, d_desc,
                                     overlap ? nullptr : d_nodes, d_n, nullptr);
@@ -998,8 +981,8 @@ int vslam_frontend_sequence(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, in
     if (overlap)
         if ((rc = vs_defer_tree_build(ctx, d_xy, d_n, frames, kp_stride, d_nodes))) return rc;
     const size_t one = (size_t)kp_stride;
-    rc = vslam_match_features(ctx, d_xy, d_desc, d_n, d_xy + 2 * one, d_desc + VSLAM_DESC_BYTES * one, d_n + 1,
-                              frames - 1, kp_stride, d_seeds, hyp, threshold, d_matches, d_best, d_F, nullptr);
+    rc = vs_match_features(ctx, d_xy, d_desc, d_n, d_xy + 2 * one, d_desc + VSLAM_DESC_BYTES * one, d_n + 1,
+                           frames - 1, kp_stride, d_seeds, hyp, threshold, d_matches, d_best, d_F, nullptr, raw_ready);
     if (rc == VSLAM_OK && overlap && ctx->aux_job) rc = vs_aux_job_point(ctx, ctx->aux_job_at);   // see vslam_frontend_pairs
     if (overlap) VS_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return rc;

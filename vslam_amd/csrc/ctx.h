@@ -34,11 +34,8 @@ struct vslam_ctx {
     // uploads (frame ingest) run on their own stream; ev_upload marks the last one enqueued
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_upload = nullptr;
-    // raw mt19937 outputs produced ahead of time on the auxiliary stream (vslam_frontend_pairs / _sequence): valid for
-    // exactly the (seeds, batch, hyp) recorded here until vslam_match_features consumes them
+    // recorded behind the raw mt19937 outputs produced ahead of time on the auxiliary stream (vslam_frontend_pairs / _sequence)
     hipEvent_t ev_raw = nullptr;
-    const uint32_t *raw_seeds = nullptr;
-    int raw_batch = 0, raw_hyp = 0;
     // An independent stage (the k-d build: an output of the path, nobody's input) that vslam_frontend_pairs / _sequence hand
     // to the matching stages to be forked onto the auxiliary stream at the point where it disturbs them least:
     // aux_job_at = 1 after the matcher, 2 after the set mapping, 3 after the solves, 4 after the screen (0: at once / none).  vs_aux_job_point(ctx, k)
@@ -53,11 +50,6 @@ struct vslam_ctx {
     bool lazy_streams = false;   // the copy stream is made on first use
     int solve_split = 0;        // VSLAM_RANSAC_SOLVE_SPLIT (read when the context is made): 0 one solve kernel, 4 / 5 sweeps + closing kernel
     bool sets_prefetch = true;  // VSLAM_SETS_PREFETCH: the raw mt19937 outputs generated ahead of time on the auxiliary stream
-    bool fork_after_eigen = false;   // transient: good_features records ev_fork once the response kernel is queued
-    bool rbrief_table_ready = false; // transient: the rotated rBRIEF table of the coming describe call is already queued
-    int img_pitch = 0;               // transient (vslam_extract_features): bytes per row of the call's internal gray / blurred planes when that is
-                                     // not the width -- a width that is no multiple of 4 gets rows of a multiple of 16 bytes whose tail holds the
-                                     // REFLECT_101 continuation of the row, so that the dword kernels take it; 0: rows are `width` bytes
     int ransac_min_matches = VSLAM_SET_SIZE;   // VSLAM_OPT_RANSAC_MIN_MATCHES
     int ransac_min_items = VSLAM_SET_SIZE;     // VSLAM_OPT_RANSAC_MIN_ITEMS: indices drawn per 8-wide set
     int ransac_solver = 0;                      // VSLAM_OPT_RANSAC_SOLVER: 0 exact Jacobi replay, 1 Gram / MFMA (not bit-exact)
@@ -126,9 +118,16 @@ struct VsProfScope {
     ~VsProfScope();
 };
 
+// Launchers queue on ctx->stream: this points it at another stream (the auxiliary one) until the end of the scope, on every
+// return path.  Forking onto that stream and joining it again stay the caller's job.
+struct VsStreamScope {
+    vslam_ctx *ctx;
+    hipStream_t saved;
+    VsStreamScope(vslam_ctx *c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+    ~VsStreamScope() { ctx->stream = saved; }
+};
+
 static inline int vs_div_up(int a, int b) { return (a + b - 1) / b; }
-// bytes per row of the internal gray / blurred planes of the running extract call (vslam_ctx::img_pitch)
-static inline int vs_pitch(const vslam_ctx *ctx, int w) { return ctx->img_pitch > 0 ? ctx->img_pitch : w; }
 
 // A/B switches (slower kernel variants, stream arrangements, tile shapes measured and not chosen) exist only in the
 // EXPERIMENTS build of the library (-DVSLAM_EXPERIMENTS -> libvslam_amd_exp.so, which tools/ab_*.py and the variant tests load
@@ -168,6 +167,9 @@ static inline int vs_stream_segments(int h, int frames, int strips) {
 }
 
 // ---- stage launchers implemented in the .hip files (all async on ctx->stream) ----
+// `pitch` (the image stages): bytes per row of the gray / blurred planes, >= w.  Packed rows pass w; a width that is no multiple
+// of 4 may get rows of a multiple of 16 bytes whose tail holds the row's BORDER_REFLECT_101 continuation, so that the dword
+// kernels take them (vs_padded_pitch in capi.hip).
 int vs_launch_match(vslam_ctx *ctx, const uint8_t *d1, const int32_t *n1, const uint8_t *d2,
                     const int32_t *n2, int batch, int kp_stride, int32_t *pairs, int32_t *m,
                     int32_t *knn);
@@ -200,8 +202,8 @@ int vs_launch_kdtree_nearest(vslam_ctx *ctx, const int32_t *nodes, const float *
 int vs_launch_kdtree_cell_table(vslam_ctx *ctx, const int32_t *nodes, const float *xy, const int32_t *n, int batch,
                                 int kp_stride, int slots, uint32_t *table, int32_t *ok);
 int vs_launch_bgr2gray(vslam_ctx *ctx, const uint8_t *bgr, int frames, int w, int h, int stride,
-                       uint8_t *gray);
-int vs_launch_min_eigen(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, float *eig,
+                       uint8_t *gray, int pitch);
+int vs_launch_min_eigen(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, float *eig,
                         uint32_t *frame_max_bits);
 // per-frame counters of the corner pipeline: one zero-initialised block (select.hip lays it out)
 struct VsCornerCounters {
@@ -233,7 +235,8 @@ __device__ __forceinline__ int vs_pool_used(const VsCornerPool &p) {
     return used < p.slots ? used : p.slots;
 }
 #endif
-int vs_launch_pool_candidates(vslam_ctx *ctx, const uint8_t *gray, int w, int h, double quality, const VsCornerPool &pool);
+int vs_launch_pool_candidates(vslam_ctx *ctx, const uint8_t *gray, int w, int h, int pitch, double quality,
+                              const VsCornerPool &pool);
 size_t vs_response_hist_words(int frames);
 // `gray` still to be formed from a 3-byte image (cvtColor is then the detector's job: fused into its first kernel when
 // the layout allows, a launch of its own otherwise)
@@ -241,25 +244,29 @@ struct VsBgrSource {
     const uint8_t *data;
     int stride;   // bytes per row
 };
-int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, double quality,
+int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, double quality,
                                   float *eig, const VsCornerCounters &c, unsigned long long *keys,
                                   unsigned long long *keys2, size_t key_cap, uint32_t n_safe, int *raw_list,
                                   const VsBgrSource *bgr = nullptr);
-int vs_launch_corner_exact(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, const VsCornerCounters &c,
+int vs_launch_corner_exact(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, const VsCornerCounters &c,
                            const unsigned long long *keys, unsigned long long *keys2, size_t key_cap, uint32_t n_safe,
                            int mode);
-int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h,
+// fork_aux: record ev_fork and make the auxiliary stream wait on it once the response kernels are queued (the caller runs an
+// independent stage there beside the selection)
+int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch,
                             int max_corners, double quality, double min_distance, int kp_stride,
-                            float *xy, int32_t *n, const VsBgrSource *bgr = nullptr);
-int vs_launch_gaussian7(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, uint8_t *out);
+                            float *xy, int32_t *n, const VsBgrSource *bgr = nullptr, bool fork_aux = false);
+int vs_launch_gaussian7(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, uint8_t *out);
 int vs_launch_gray_pad(vslam_ctx *ctx, const uint8_t *src, int frames, int w, int h, uint8_t *dst, int pitch);
 int vs_launch_gray_unpad(vslam_ctx *ctx, const uint8_t *src, int frames, int w, int h, int pitch, uint8_t *dst);
 int vs_launch_gaussian7_rows(vslam_ctx *ctx, const uint8_t *src, uint8_t *dst, int frames, size_t frame_pitch, int w, int h,
                              int y_begin, int y_end);
-int vs_launch_rbrief_rotate(vslam_ctx *ctx, const int8_t *pattern, float ca, float sa);
-int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, int w, int h,
+// the rotated rBRIEF table (513 words) queued ahead of a describe call; rotated_table: that table, nullptr to rotate it there
+int vs_launch_rbrief_rotate(vslam_ctx *ctx, const int8_t *pattern, float ca, float sa, const int32_t **table);
+int vs_launch_orb_describe(vslam_ctx *ctx, const uint8_t *blurred, int frames, int w, int h, int pitch,
                            const float *xy_in, const int32_t *n_in, int kp_stride, float ca, float sa,
-                           const int8_t *pattern, float *xy_out, uint8_t *desc, int32_t *n_out);
+                           const int8_t *pattern, const int32_t *rotated_table, float *xy_out, uint8_t *desc,
+                           int32_t *n_out);
 int vs_launch_extract_grid(vslam_ctx *ctx, uint8_t *bgr, int frames, int w, int h, int stride, int nrows, int ncols,
                            const int8_t *pattern, int kp_cap, float *xy, uint8_t *desc, float *angle_octave,
                            int32_t *n_out);

@@ -123,14 +123,13 @@ int vs_launch_gray_unpad(vslam_ctx *ctx, const uint8_t *src, int frames, int w, 
 }
 
 int vs_launch_bgr2gray(vslam_ctx *ctx, const uint8_t *bgr, int frames, int w, int h, int stride,
-                       uint8_t *gray) {
+                       uint8_t *gray, int pitch) {
     VS_REQUIRE(ctx, bgr && gray, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, frames > 0 && w > 0 && h > 0 && stride >= 3 * w, VSLAM_ERR_INVALID);
     const int aligned = (stride % 4 == 0) && (w % 4 == 0) && ((reinterpret_cast<uintptr_t>(bgr) & 3) == 0) &&
                         ((reinterpret_cast<uintptr_t>(gray) & 3) == 0) && (((size_t)h * stride) % 4 == 0);
     VsProfScope ps(ctx, "bgr2gray_kernel");
-    const int pitch = vs_pitch(ctx, w);
-    if (pitch != w) {   // padded rows (vslam_ctx::img_pitch)
+    if (pitch != w) {   // padded rows with a mirrored tail
         VS_REQUIRE(ctx, pitch % 4 == 0 && pitch >= w + 3 && pitch - w < w - 1 && (reinterpret_cast<uintptr_t>(gray) & 3) == 0, VSLAM_ERR_INVALID);
         dim3 pgrid(vs_div_up((pitch / 4) * h, 256), frames);
         bgr2gray_padded_kernel<<<pgrid, 256, 0, ctx->stream>>>(bgr, w, h, stride, gray, pitch);

@@ -1449,12 +1449,8 @@ int vs_launch_extract_grid(vslam_ctx *ctx, uint8_t *bgr, int frames, int w, int 
     }
     {   // ORB::compute (:43): per-level blur of the outlined frame's pyramid, steered BRIEF
         VsProfScope ps(ctx, "orb_compute_kernels");
-        if (w >= 4 && h >= 4) {
-            ctx->img_pitch = G.gp != w ? G.gp : 0;   // padded rows: the streaming blur takes them as they are (blur.hip)
-            rc = vs_launch_gaussian7(ctx, gray, frames, w, h, blur0);
-            ctx->img_pitch = 0;
-            if (rc) return rc;
-        }
+        if (w >= 4 && h >= 4)   // padded rows (G.gp > w): the streaming blur takes them as they are (blur.hip)
+            if ((rc = vs_launch_gaussian7(ctx, gray, frames, w, h, G.gp, blur0))) return rc;
         // levels >= 1 as images of fstride x (lh + 6) bytes whose margins hold the reflect values: rows 3 .. lh + 2 through the
         // streaming blur (what it writes into the margin columns of fblur is never read)
         for (int l = 1; l < G.nlv; l++)

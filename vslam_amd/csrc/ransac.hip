@@ -2399,7 +2399,6 @@ int vs_launch_ransac_sets(vslam_ctx *ctx, const uint32_t *seeds, const int32_t *
     uint32_t *raw = nullptr;
     int rc = vs_arena_get(ctx, "mf.raw", sizeof(uint32_t) * vs_ransac_raw_words(hyp) * (size_t)batch, (void **)&raw);
     if (rc) return rc;
-    ctx->raw_seeds = nullptr;   // the buffer is being rewritten: whatever was produced ahead of time is gone
     if ((rc = vs_launch_ransac_mt(ctx, seeds, batch, hyp, raw))) return rc;
     return vs_launch_ransac_map(ctx, m, batch, hyp, raw, sets, draws);
 }

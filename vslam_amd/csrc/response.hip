@@ -2,7 +2,7 @@
 // and the 3x3-local-maximum candidates for gfx950.
 //   min_eigen_tiered_kernel   the front-end path, tier 1: a certified bound of the response for every pixel + the list of pixels
 //                             that can matter, one streaming pass (BGR form: cvtColor inside; gray form: rows of a multiple of 4
-//                             bytes, i.e. width % 4 == 0 or padded rows with a mirrored tail, vslam_ctx::img_pitch)
+//                             bytes, i.e. width % 4 == 0 or padded rows with a mirrored tail, the launchers' `pitch`)
 //   corner_exact_kernel       tier 2: the oracle's arithmetic for the listed pixels
 //   min_eigen_v4_kernel       response only, tiled (vslam_min_eigen, the pool's rerun; width % 4 == 0)
 //   min_eigen_kernel          response only, any width and row pitch
@@ -350,7 +350,7 @@ struct TierArgs {
     uint32_t *count;
     size_t cap;
     int w, h, ys, ye, x, steps;
-    int bstride;                     // bytes per row of src (the gray form's rows may be longer than w: vslam_ctx::img_pitch)
+    int bstride;                     // bytes per row of src (the gray form's rows may be longer than w: the launcher's `pitch`)
     uint8_t *gout;                   // BGR input: this frame's gray image (written for the rows [ys, ye))
     const uint32_t *halo;            // BGR input, LDS: per row of the wave's segment the gray pixels left / right of the strip
     uint32_t voff_l, voff_c, voff_r;
@@ -1043,18 +1043,18 @@ __global__ __launch_bounds__(kCT) void corner_candidates_kernel(
 
 }  // namespace
 
-int vs_launch_min_eigen(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, float *eig,
+int vs_launch_min_eigen(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, float *eig,
                         uint32_t *frame_max_bits) {
     VS_REQUIRE(ctx, gray && eig, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, frames > 0 && w >= 3 && h >= 3, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, frames > 0 && w >= 3 && h >= 3 && pitch >= w, VSLAM_ERR_INVALID);
     if (frame_max_bits) VS_HIP(ctx, hipMemsetAsync(frame_max_bits, 0, sizeof(uint32_t) * (size_t)frames, ctx->stream));
     VsProfScope ps(ctx, "min_eigen_kernel");
-    if (w % 4 == 0 && vs_pitch(ctx, w) == w && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0) && ((reinterpret_cast<uintptr_t>(eig) & 15) == 0)) {
+    if (w % 4 == 0 && pitch == w && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0) && ((reinterpret_cast<uintptr_t>(eig) & 15) == 0)) {
         dim3 grid(vs_div_up(w, kE4W), vs_div_up(h, kE4H), frames);
         min_eigen_v4_kernel<<<grid, 256, 0, ctx->stream>>>(gray, w, h, eig, frame_max_bits, VsCornerPool{});
     } else {
         dim3 grid(vs_div_up(w, kETW), vs_div_up(h, kETH), frames);
-        min_eigen_kernel<<<grid, kET, 0, ctx->stream>>>(gray, w, h, vs_pitch(ctx, w), eig, frame_max_bits, VsCornerPool{});
+        min_eigen_kernel<<<grid, kET, 0, ctx->stream>>>(gray, w, h, pitch, eig, frame_max_bits, VsCornerPool{});
     }
     VS_HIP(ctx, hipGetLastError());
     return VSLAM_OK;
@@ -1067,21 +1067,20 @@ int vs_launch_min_eigen(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, 
 //   otherwise (tiled detector): eig filled, keys[f][0 .. counts[f]) = exact keys; raw_list = 0.
 size_t vs_response_hist_words(int frames) { return (size_t)frames * kTierBins; }
 
-int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, double quality,
+int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, double quality,
                                   float *eig, const VsCornerCounters &c, unsigned long long *keys,
                                   unsigned long long *keys2, size_t key_cap, uint32_t n_safe, int *raw_list,
                                   const VsBgrSource *bgr) {
     int rc;
-    const int gp = vs_pitch(ctx, w);   // bytes per gray row: w, or longer with a mirrored tail (vslam_ctx::img_pitch)
-    const bool fused = (gp % 4 == 0) && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0);
+    const bool fused = (pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0);
     *raw_list = fused ? 1 : 0;
     // the gray image has not been formed yet (bgr != nullptr): the two-tier detector does it on the way for packed gray
     // rows (width % 4 == 0, any row stride of the source), a cvtColor launch in front writes padded rows otherwise
     static const char *const nofuse = VS_EXPERIMENT_ENV("VSLAM_NO_GRAY_FUSION");
-    const bool from_bgr = bgr && fused && gp == w && !nofuse &&
+    const bool from_bgr = bgr && fused && pitch == w && !nofuse &&
                           vs_div_up(h, vs_stream_segments(h, frames, vs_div_up(w, kSW))) + 6 <= kTierMaxSteps;
     if (bgr && !from_bgr)
-        if ((rc = vs_launch_bgr2gray(ctx, bgr->data, frames, w, h, bgr->stride, const_cast<uint8_t *>(gray)))) return rc;
+        if ((rc = vs_launch_bgr2gray(ctx, bgr->data, frames, w, h, bgr->stride, const_cast<uint8_t *>(gray), pitch))) return rc;
     if (fused) {
         if (from_bgr) {
             VsProfScope ps(ctx, "min_eigen_kernel");
@@ -1099,14 +1098,14 @@ int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frame
             const int seg_rows = vs_div_up(h, segs);
             const int per_frame = strips * vs_div_up(segs, 4);
             min_eigen_tiered_kernel<false><<<vs_xcd_grid(frames, per_frame), 256, 0, ctx->stream>>>(
-                gray, gp, nullptr, w, h, c.low, c.hist, quality, keys, c.counts, key_cap, seg_rows, frames, strips, per_frame);
+                gray, pitch, nullptr, w, h, c.low, c.hist, quality, keys, c.counts, key_cap, seg_rows, frames, strips, per_frame);
         }
         // A frame whose maximum response is not positive has no corners (its threshold max * quality lies at or above
         // every response, THRESH_TOZERO clears the image and zeros are not corners); the selection's exact threshold
         // drops every key of such a frame, so it needs no special handling here.
-        if ((rc = vs_launch_corner_exact(ctx, gray, frames, w, h, c, keys, keys2, key_cap, n_safe, 0))) return rc;
+        if ((rc = vs_launch_corner_exact(ctx, gray, frames, w, h, pitch, c, keys, keys2, key_cap, n_safe, 0))) return rc;
     } else {
-        if ((rc = vs_launch_min_eigen(ctx, gray, frames, w, h, eig, c.fmax))) return rc;
+        if ((rc = vs_launch_min_eigen(ctx, gray, frames, w, h, pitch, eig, c.fmax))) return rc;
         VsProfScope ps(ctx, "corner_candidates_kernel");
         dim3 grid(vs_div_up(w, kCTW), vs_div_up(h, kCTH), frames);
         corner_candidates_kernel<<<grid, kCT, 0, ctx->stream>>>(eig, w, h, c.fmax, quality, keys, c.counts, key_cap, VsCornerPool{});
@@ -1119,11 +1118,12 @@ int vs_launch_response_candidates(vslam_ctx *ctx, const uint8_t *gray, int frame
 // selection needs the per-pixel maps -- are redone with the plain pipeline on whole-image scratch: exact response of every
 // pixel and the frame maximum (by slot), then every candidate's exact key.  Always queued; returns at once when the pool
 // is empty (two launches of a few thousand idle workgroups).
-int vs_launch_pool_candidates(vslam_ctx *ctx, const uint8_t *gray, int w, int h, double quality, const VsCornerPool &pool) {
+int vs_launch_pool_candidates(vslam_ctx *ctx, const uint8_t *gray, int w, int h, int pitch, double quality,
+                              const VsCornerPool &pool) {
     VsProfScope ps(ctx, "corner_rerun_kernels");
-    if (vs_pitch(ctx, w) != w) {   // padded gray rows: the any-width kernel reads them
+    if (pitch != w) {   // padded gray rows: the any-width kernel reads them
         dim3 grid(vs_div_up(w, kETW), vs_div_up(h, kETH), pool.slots);
-        min_eigen_kernel<<<grid, kET, 0, ctx->stream>>>(gray, w, h, vs_pitch(ctx, w), pool.eig, pool.fmax, pool);
+        min_eigen_kernel<<<grid, kET, 0, ctx->stream>>>(gray, w, h, pitch, pool.eig, pool.fmax, pool);
     } else {
         dim3 grid(vs_div_up(w, kE4W), vs_div_up(h, kE4H), pool.slots);
         min_eigen_v4_kernel<<<grid, 256, 0, ctx->stream>>>(gray, w, h, pool.eig, pool.fmax, pool);
@@ -1136,14 +1136,14 @@ int vs_launch_pool_candidates(vslam_ctx *ctx, const uint8_t *gray, int w, int h,
 }
 
 // mode 0: the entries above the cut -> keys2 / count2; mode 1: every entry of the frames flagged in c.need -> keys2 / count3
-int vs_launch_corner_exact(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, const VsCornerCounters &c,
+int vs_launch_corner_exact(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch, const VsCornerCounters &c,
                            const unsigned long long *keys, unsigned long long *keys2, size_t key_cap, uint32_t n_safe,
                            int mode) {
     VsProfScope ps(ctx, mode == 0 ? "corner_exact_kernel" : "corner_rerun_kernels");
     static const char *const pf_env = VS_EXPERIMENT_ENV("VSLAM_CORNER_EXACT_WGS");
     const int per_frame = pf_env ? atoi(pf_env) : 4;
     corner_exact_kernel<<<vs_xcd_grid(frames, per_frame), 256, 0, ctx->stream>>>(
-        gray, w, h, vs_pitch(ctx, w), keys, c.counts, key_cap, c.hist, c.low, n_safe, keys2, mode == 0 ? c.count2 : c.count3, c.fmax, c.cutkey,
+        gray, w, h, pitch, keys, c.counts, key_cap, c.hist, c.low, n_safe, keys2, mode == 0 ? c.count2 : c.count3, c.fmax, c.cutkey,
         c.need, mode, frames, per_frame);
     VS_HIP(ctx, hipGetLastError());
     return VSLAM_OK;

@@ -824,11 +824,11 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
 }  // namespace
 
-int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h,
+int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int w, int h, int pitch,
                             int max_corners, double quality, double min_distance, int kp_stride,
-                            float *xy, int32_t *n, const VsBgrSource *bgr) {
+                            float *xy, int32_t *n, const VsBgrSource *bgr, bool fork_aux) {
     VS_REQUIRE(ctx, gray && xy && n, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, frames > 0 && w >= 3 && h >= 3, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, frames > 0 && w >= 3 && h >= 3 && pitch >= w, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, max_corners > 0 && max_corners <= kp_stride, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, min_distance < 64.0, VSLAM_ERR_CAPACITY);
     VS_REQUIRE(ctx, (size_t)w * h < (1u << 28), VSLAM_ERR_CAPACITY);   // pixel offsets share their word with 4 flag bits (image_common.h)
@@ -847,7 +847,7 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
     // than it has slots, those frames get no corners and vslam_ctx_synchronize reports VSLAM_ERR_CAPACITY.
     // Gray rows that are no multiple of 4 bytes (a caller's packed image of such a width that nobody padded: widths below 64)
     // run the plain pipeline on whole-image buffers for every frame.
-    const bool two_tier = (vs_pitch(ctx, w) % 4 == 0) && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0);   // (as vs_launch_response_candidates decides)
+    const bool two_tier = (pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(gray) & 3) == 0);   // (as vs_launch_response_candidates decides)
     size_t key_cap = px;
     if (two_tier && ctx->corner_list_cap >= 0) {
         const size_t want = ctx->corner_list_cap > 0 ? (size_t)ctx->corner_list_cap : 16 * (size_t)max_corners + 4096;
@@ -908,8 +908,8 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
                                 ? (uint32_t)((unsigned long long)max_corners * (unsigned)ctx->corner_window_pct / 100u) + 128u
                                 : 0xFFFFFFFFu;   // 0: everything
     int raw_list = 0;
-    if ((rc = vs_launch_response_candidates(ctx, gray, frames, w, h, quality, eig, c, keys, keys2, key_cap, n_safe, &raw_list, bgr))) return rc;
-    if (ctx->fork_after_eigen) {   // the caller runs an independent stage on the auxiliary stream beside the selection
+    if ((rc = vs_launch_response_candidates(ctx, gray, frames, w, h, pitch, quality, eig, c, keys, keys2, key_cap, n_safe, &raw_list, bgr))) return rc;
+    if (fork_aux) {   // the caller runs an independent stage on the auxiliary stream beside the selection
         VS_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         VS_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
     }
@@ -969,13 +969,13 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
         if (raw_list) {
             // the rerun, for the frames (if any) whose selection ran out of keys above the cut: every listed pixel is
             // evaluated, then selected from again.  Both launches return at once for the other frames.
-            if ((rc = vs_launch_corner_exact(ctx, gray, frames, w, h, c, keys, keys2, key_cap, 0u, 1))) return rc;
+            if ((rc = vs_launch_corner_exact(ctx, gray, frames, w, h, pitch, c, keys, keys2, key_cap, 0u, 1))) return rc;
             {
                 VsProfScope ps(ctx, "corner_rerun_kernels");
                 VS_SELECT_DISPATCH(1, keys2, c.count3)
             }
             // the pool's frames (usually none: three launches that return at once), redone by the plain exact pipeline
-            if ((rc = vs_launch_pool_candidates(ctx, gray, w, h, quality, pool))) return rc;
+            if ((rc = vs_launch_pool_candidates(ctx, gray, w, h, pitch, quality, pool))) return rc;
             VsProfScope ps(ctx, "corner_rerun_kernels");
             VS_SELECT_DISPATCH(2, pool.keys, pool.counts)
         }
