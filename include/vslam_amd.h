@@ -350,6 +350,86 @@ int vslam_associate_map_points(vslam_ctx *ctx, const float *d_map_points, const 
                                const uint8_t *d_obs_desc, int obs_stride, float radius,
                                uint32_t dist_threshold, int32_t *d_map_point_ids, int32_t *d_claim);
 
+/* ------------------------------------------------------------ the map, resident (PointMap + the loop between pairs)
+ * What src/vslam.cpp:60-270 carries from frame to frame, for `tracks` independent sequences advanced in lockstep (one frame
+ * step = one batch of `tracks` pairs), entirely in device memory with capacities fixed at creation (the reference's doubling
+ * `capacity` is not observable and is not copied):
+ *   pm.points / pm.size / pm.colors                 d_points [tracks][map_capacity][4] (x, y, z, 1), d_sizes [tracks],
+ *                                                   d_colors [tracks][map_capacity][3] u8
+ *   pm.frame_ids[i] / pm.frame_point_ids[i]         an observation log; vslam_map_observations writes it out as CSR lists in
+ *                                                   the reference's push order
+ *   frame.map_point_ids of every frame              d_map_point_ids [tracks][max_frames][kp_stride], -1 = none (src/Frame.cpp:73)
+ *   frame.R_t, frame.pose                           d_R_t, d_pose [tracks][max_frames][16], frame 0 = identity
+ * A map belongs to the context it was made on and is destroyed BEFORE it (vslam_map_destroy waits for the context's stream);
+ * every call is stream-ordered on that context.  vslam_map_reset / _step / _view / _observations allocate nothing;
+ * vslam_track_sequences takes its flattened seed row and the front-end's workspaces from the context's grow-only arena, like
+ * vslam_frontend_sequence.  Descriptor arrays handed to a map call are 16-byte aligned, matches and points 8-byte aligned
+ * (VSLAM_ERR_INVALID otherwise); match indices outside the frames' keypoint counts are ignored.  Frame ids count from 0 per track; `frames` = frames recorded so far (1 after create / reset: frame 0). */
+typedef struct vslam_map vslam_map;
+typedef struct vslam_map_arrays {
+    int32_t tracks, max_frames, kp_stride, map_capacity, obs_capacity;
+    int32_t frames;                  /* frames recorded so far, frame 0 included (host-side counter)                 */
+    float *d_points;                 /* [tracks][map_capacity][4]                                                     */
+    uint8_t *d_colors;               /* [tracks][map_capacity][3]                                                     */
+    int32_t *d_sizes;                /* [tracks]                                                                      */
+    int32_t *d_map_point_ids;        /* [tracks][max_frames][kp_stride]                                               */
+    float *d_R_t;                    /* [tracks][max_frames][16]                                                      */
+    float *d_pose;                   /* [tracks][max_frames][16]                                                      */
+    int32_t *d_obs_counts;           /* [tracks][map_capacity] observations per map point                             */
+    int32_t *d_n_obs;                /* [tracks] observations in all                                                  */
+} vslam_map_arrays;
+int vslam_map_create(vslam_ctx *ctx, int tracks, int max_frames, int kp_stride, int map_capacity, int obs_capacity,
+                     vslam_map **out);
+int vslam_map_destroy(vslam_map *map);
+/* Back to empty (frame 0 recorded, identity poses, no ids, no points); no reallocation. */
+int vslam_map_reset(vslam_ctx *ctx, vslam_map *map);
+/* One iteration of src/vslam.cpp:60-270 for every track, nothing leaving the device.  Inputs, all [tracks][...] batches:
+ * the features of the last and the current frame as vslam_extract_features writes them, the pair's d_matches / d_best / d_F as
+ * vslam_match_features writes them, the current frames' images d_bgr_cur [tracks][height][row_stride]; h_K HOST 3 x 3;
+ * radius 2, dist_threshold 64, reproj_threshold_sq 4 in the reference.  In stream order:
+ *   1. extract_Rt, c2 = K [R | t], R_t, pose = last.pose * R_t (:83-88; the 4 x 4 product in exact double products summed
+ *      left to right, one rounding);
+ *   2. propagation (:105-118): match (first, second) with id = last.map_point_ids[first] > 0 -- map point 0 is never
+ *      propagated, as in the reference -- sets cur.map_point_ids[second] = id (of two matches onto one `second` the later
+ *      wins) and pushes the observation (frame, second) onto map point id (both do);
+ *   3. association (:126-161) = vslam_associate_map_points over the map as it stands before this frame's new points, its
+ *      observations including those of step 2; every claim pushes an observation;
+ *   4. vslam_triangulate (c1 = [K | 0]) and vslam_reprojection_filter against the UPDATED map_point_ids;
+ *   5. add_reprojection_inliers (src/PointMap.cpp:3-34): the kept matches, ascending, become map points size .. size + k - 1
+ *      with w = 1, the observations (last frame, first), (frame, second) in that order and the colour
+ *      image.at(int(x2), int(y2)): ROW int(x), COLUMN int(y), as the reference writes it (:247).  Where that row is >= height
+ *      (or the column >= width) the reference reads outside the image or the row; (0, 0, 0) is written here.  map_point_ids are
+ *      not set for new points (the reference does not).
+ * A pair without a RANSAC winner (d_best[.][0] < 0, the items vslam_extract_Rt skips) leaves its track's map untouched for the
+ * step: R_t = identity, pose carried over, no ids (the reference would go on with an empty F: undefined).  A track for which
+ * map_capacity or obs_capacity does not suffice anywhere in the step is left the same way -- nothing partial -- and a step
+ * beyond max_frames does nothing at all; both raise the context's sticky error word (VSLAM_ERR_CAPACITY from
+ * vslam_ctx_synchronize / the pipeline ticket), as does the 16-candidate cap of the association.                            */
+int vslam_map_step(vslam_ctx *ctx, vslam_map *map, const float *d_xy_last, const uint8_t *d_desc_last, const int32_t *d_n_last,
+                   const float *d_xy_cur, const uint8_t *d_desc_cur, const int32_t *d_nodes_cur, const int32_t *d_n_cur,
+                   const int32_t *d_matches, const int32_t *d_best, const float *d_F, const uint8_t *d_bgr_cur, int width,
+                   int height, int row_stride, const float *h_K, float radius, uint32_t dist_threshold,
+                   float reproj_threshold_sq);
+/* Device pointers of the state (valid until vslam_map_destroy; contents as of the work queued so far). */
+int vslam_map_view(vslam_map *map, vslam_map_arrays *out);
+/* pm.frame_ids / pm.frame_point_ids as CSR, stream-ordered: d_offsets [tracks][map_capacity + 1] (entries past a track's size
+ * repeat its total), d_frame_ids / d_point_ids [tracks][obs_capacity]: map point i of track b observed by
+ * (d_frame_ids[b][o], d_point_ids[b][o]) for o in [d_offsets[b][i], d_offsets[b][i + 1]), in the reference's push order.
+ * Slots past a track's total are not written.                                                                            */
+int vslam_map_observations(vslam_ctx *ctx, vslam_map *map, int32_t *d_offsets, int32_t *d_frame_ids, int32_t *d_point_ids);
+/* The loop for resident video: d_bgr [tracks][frames][height][row_stride]; d_seeds [tracks][frames - 1].  Resets the map,
+ * extracts all tracks * frames frames once and matches every consecutive pair as one batch -- vslam_frontend_sequence over the
+ * flattened frames (index track * frames + f), so that no existing translation unit changes; the tracks - 1 pairs that
+ * straddle two tracks are computed and ignored (1 / frames of the matching time) -- then frames - 1 map steps.  Per-frame
+ * outputs [tracks * frames] slots and per-pair outputs [tracks * frames - 1] slots are the caller's, as in
+ * vslam_frontend_sequence with frames = tracks * frames: pair (track, f -> f + 1) is slot track * frames + f, so the records
+ * path keeps working.  kp_stride is the map's (<= 8160: the trees are needed).  Steps beyond max_frames do nothing and raise the
+ * error word, like vslam_map_step.                                                                                        */
+int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, int frames, int width, int height,
+                          int row_stride, const vslam_extract_params *params, const uint32_t *d_seeds, int hyp, float threshold,
+                          const float *h_K, float radius, uint32_t dist_threshold, float reproj_threshold_sq, float *d_xy,
+                          uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches, int32_t *d_best, float *d_F);
+
 /* ------------------------------------------------------------------ pipeline */
 /* match_features(frame1, frame2, rf, matches, F), src/Frame.cpp:82-105, for a batch of pairs
  * whose features are already on the device: match -> sets -> RANSAC -> inlier matches.

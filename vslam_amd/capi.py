@@ -28,6 +28,8 @@ SYMBOLS = [
     "vslam_kdtree_radius", "vslam_kdtree_nearest", "vslam_kdtree_cell_table", "vslam_extract_features", "vslam_extract_features_grid", "vslam_triangulate_points", "vslam_frontend_pairs_pose", "vslam_pipeline_batches_redone", "vslam_corner_stats", "vslam_bgr2gray", "vslam_min_eigen",
     "vslam_good_features", "vslam_gaussian7", "vslam_orb_describe", "vslam_extract_Rt", "vslam_triangulate", "vslam_associate_map_points", "vslam_reprojection_filter",
     "vslam_match_features",
+    "vslam_map_create", "vslam_map_destroy", "vslam_map_reset", "vslam_map_step", "vslam_map_view", "vslam_map_observations",
+    "vslam_track_sequences",
     "vslam_frontend_pairs", "vslam_frontend_sequence", "vslam_pack_records",
     "vslam_host_alloc", "vslam_host_free", "vslam_upload_async", "vslam_upload_fence", "vslam_upload_wait", "vslam_download_async",
     "vslam_shard_range", "vslam_multi_create", "vslam_multi_destroy", "vslam_multi_size", "vslam_multi_ctx", "vslam_multi_last_error",
@@ -46,6 +48,13 @@ class ExtractParams(C.Structure):
 class PoseOutputs(C.Structure):   # vslam_pose_outputs
     _fields_ = [("d_R", C.c_void_p), ("d_t", C.c_void_p), ("d_c2", C.c_void_p), ("d_points4d", C.c_void_p),
                 ("d_inlier_idx", C.c_void_p), ("d_n_inliers", C.c_void_p), ("d_error", C.c_void_p)]
+
+
+class MapArrays(C.Structure):   # vslam_map_arrays
+    _fields_ = [("tracks", C.c_int32), ("max_frames", C.c_int32), ("kp_stride", C.c_int32), ("map_capacity", C.c_int32),
+                ("obs_capacity", C.c_int32), ("frames", C.c_int32), ("d_points", C.c_void_p), ("d_colors", C.c_void_p),
+                ("d_sizes", C.c_void_p), ("d_map_point_ids", C.c_void_p), ("d_R_t", C.c_void_p), ("d_pose", C.c_void_p),
+                ("d_obs_counts", C.c_void_p), ("d_n_obs", C.c_void_p)]
 
 
 class VslamError(RuntimeError):
@@ -555,6 +564,129 @@ class Context:
             _ptr(seeds), C.c_int(hyp), C.c_float(threshold), _ptr(out["xy"]), _ptr(out["desc"]), _ptr(out["nodes"]),
             _ptr(out["n"]), _ptr(out["matches"]), _ptr(out["best"]), _ptr(out["F"])))
         return out
+
+
+    def track_sequences(self, pmap, bgr, max_corners, cos_a, sin_a, pattern, seeds, hyp, threshold, K, radius=2.0, dist_threshold=64,
+                         thr_sq=4.0, out=None, width=None):
+        """vslam_track_sequences: bgr (tracks, frames, H, W, 3), or (tracks, frames, H, row_bytes) together with `width`; seeds
+        (tracks, frames - 1) int32 bit patterns.  Per-frame outputs have tracks * frames slots, per-pair outputs tracks * frames - 1
+        (pair (t, f -> f + 1) at t * frames + f); the map itself is read through pmap.view() / pmap.observations()."""
+        import numpy as np
+        torch = self.torch
+        if bgr.dim() == 4:
+            T, Fr, H, row_bytes = bgr.shape
+            W = int(width)
+            assert row_bytes >= 3 * W
+        else:
+            T, Fr, H, W, _ = bgr.shape
+            row_bytes = 3 * W
+        assert T == pmap.tracks and tuple(seeds.shape) == (T, Fr - 1)
+        Kp = pmap.kp_stride
+        dev = bgr.device
+        N = T * Fr
+        if out is None:
+            out = dict(xy=torch.zeros((N, Kp, 2), dtype=torch.float32, device=dev),
+                       desc=torch.zeros((N, Kp, 32), dtype=torch.uint8, device=dev),
+                       nodes=torch.full((N, Kp), -1, dtype=torch.int32, device=dev),
+                       n=torch.zeros((N,), dtype=torch.int32, device=dev),
+                       matches=torch.zeros((N - 1, Kp, 2), dtype=torch.int32, device=dev),
+                       best=torch.zeros((N - 1, 4), dtype=torch.int32, device=dev),
+                       F=torch.zeros((N - 1, 9), dtype=torch.float32, device=dev))
+        self._ready()
+        p = self._params(max_corners, cos_a, sin_a, pattern)
+        Kh = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+        self._check(self.lib.vslam_track_sequences(
+            self.handle, pmap.handle, _ptr(bgr), C.c_int(Fr), C.c_int(W), C.c_int(H), C.c_int(row_bytes), C.byref(p), _ptr(seeds),
+            C.c_int(hyp), C.c_float(threshold), Kh.ctypes.data_as(C.c_void_p), C.c_float(radius), C.c_uint32(dist_threshold),
+            C.c_float(thr_sq), _ptr(out["xy"]), _ptr(out["desc"]), _ptr(out["nodes"]), _ptr(out["n"]), _ptr(out["matches"]),
+            _ptr(out["best"]), _ptr(out["F"])))
+        return out
+
+
+class PointMap:
+    """A vslam_map: the reference's PointMap and per-frame map_point_ids / R_t / pose for `tracks` sequences, resident on the
+    context's device.  `ctx` is a Context (a Pipeline slot's context included)."""
+
+    def __init__(self, ctx, tracks, max_frames, kp_stride, map_capacity, obs_capacity):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.tracks, self.max_frames, self.kp_stride = tracks, max_frames, kp_stride
+        self.map_capacity, self.obs_capacity = map_capacity, obs_capacity
+        self.handle = C.c_void_p()
+        ctx._check(self.lib.vslam_map_create(ctx.handle, C.c_int(tracks), C.c_int(max_frames), C.c_int(kp_stride),
+                                             C.c_int(map_capacity), C.c_int(obs_capacity), C.byref(self.handle)))
+
+    @classmethod
+    def create(cls, ctx, tracks, max_frames, kp_stride, map_capacity, obs_capacity):
+        return cls(ctx, tracks, max_frames, kp_stride, map_capacity, obs_capacity)
+
+    def reset(self):
+        self.ctx._check(self.lib.vslam_map_reset(self.ctx.handle, self.handle))
+
+    def step(self, last, cur, pair, bgr_cur, K, radius=2.0, dist_threshold=64, thr_sq=4.0, width=None):
+        """last / cur: dicts of xy, desc, nodes, n ([tracks][...] as extract_features returns them); pair: matches, best, F as
+        match_features returns them; bgr_cur (tracks, H, W, 3), or (tracks, H, row_bytes) together with `width`."""
+        import numpy as np
+        if bgr_cur.dim() == 3:
+            _, H, row_bytes = bgr_cur.shape
+            W = int(width)
+        else:
+            _, H, W, _ = bgr_cur.shape
+            row_bytes = 3 * W
+        Kh = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_map_step(
+            self.ctx.handle, self.handle, _ptr(last["xy"]), _ptr(last["desc"]), _ptr(last["n"]), _ptr(cur["xy"]), _ptr(cur["desc"]),
+            _ptr(cur["nodes"]), _ptr(cur["n"]), _ptr(pair["matches"]), _ptr(pair["best"]), _ptr(pair["F"]), _ptr(bgr_cur),
+            C.c_int(W), C.c_int(H), C.c_int(row_bytes), Kh.ctypes.data_as(C.c_void_p), C.c_float(radius),
+            C.c_uint32(dist_threshold), C.c_float(thr_sq)))
+
+    def arrays(self):
+        a = MapArrays()
+        self.ctx._check(self.lib.vslam_map_view(self.handle, C.byref(a)))
+        return a
+
+    def view(self):
+        """Host copies (numpy) of the state, after waiting for the context's stream (the error word is left alone)."""
+        import numpy as np
+        a = self.arrays()
+        self.ctx._check(self.lib.vslam_ctx_wait(self.ctx.handle))
+        T, Fr, Kp, M = self.tracks, self.max_frames, self.kp_stride, self.map_capacity
+
+        def get(ptr, shape, dtype):
+            h = np.empty(shape, dtype)
+            self.ctx._check(self.lib.vslam_copy_d2h(self.ctx.handle, h.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(h.nbytes)))
+            return h
+        return dict(frames=int(a.frames), points=get(a.d_points, (T, M, 4), np.float32), colors=get(a.d_colors, (T, M, 3), np.uint8),
+                    sizes=get(a.d_sizes, (T,), np.int32), map_point_ids=get(a.d_map_point_ids, (T, Fr, Kp), np.int32),
+                    R_t=get(a.d_R_t, (T, Fr, 16), np.float32), pose=get(a.d_pose, (T, Fr, 16), np.float32),
+                    obs_counts=get(a.d_obs_counts, (T, M), np.int32), n_obs=get(a.d_n_obs, (T,), np.int32))
+
+    def observations(self):
+        """(offsets [tracks][map_capacity + 1], frame_ids, point_ids [tracks][obs_capacity]) as cuda tensors, stream-ordered;
+        slots past a track's total hold -1."""
+        torch = self.ctx.torch
+        dev = self.ctx.device
+        off = torch.zeros((self.tracks, self.map_capacity + 1), dtype=torch.int32, device=dev)
+        fr = torch.full((self.tracks, self.obs_capacity), -1, dtype=torch.int32, device=dev)
+        pt = torch.full((self.tracks, self.obs_capacity), -1, dtype=torch.int32, device=dev)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_map_observations(self.ctx.handle, self.handle, _ptr(off), _ptr(fr), _ptr(pt)))
+        return off, fr, pt
+
+    def close(self):
+        """Before the context's close(): vslam_map_destroy waits for the context's stream.  After it the map is not touched
+        (the handle is dropped; a context that is gone cannot be waited for)."""
+        if self.handle:
+            if self.ctx.handle:
+                self.lib.vslam_map_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class MultiDevice:

@@ -305,3 +305,99 @@ def frames_torch_photo(seed, n_pairs, width, height, device, npz=None):
         ty = k * (cy + dy - sa * cx - ca * cy) + oy
         out[n_pairs + p] = sample(img, a_, b_, c_, d_, tx, ty)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- short sequences
+def _sequence_plan(seed, track, frames, width, height, motion):
+    """Texture and per-frame warp of one track, all integers: (base texture (H2, W2) float32, pad, list of per-frame
+    (a, b, c, d, tx, ty) in 16.16 fixed point, per-pixel parallax maps (dx, dy) in 16.16 per frame step, noise rng)."""
+    rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(track), 0x5E9])
+    pad = 32
+    H2, W2 = height + 2 * pad, width + 2 * pad
+    base = np.zeros((H2, W2), np.float32)
+    for c, amp in ((16, 70.0), (24, 50.0), (10, 25.0)):          # the texture recipe of frames_torch_hard
+        gh, gw = H2 // c + 2, W2 // c + 2
+        grid = ((rng.random((gh, gw)) * 2 - 1) * amp).astype(np.float32)
+        up = grid.repeat(c, 0).repeat(c, 1)
+        base += up[3:3 + H2, 5:5 + W2]
+    base = np.clip(128 + base, 8, 247)
+    Q = 1 << 16
+    theta = float(rng.random() * 2 - 1) * 0.12 * motion * math.pi / 180.0      # rotation per frame step
+    sx, sy = float(rng.random() * 2 - 1) * 0.9 * motion, float(rng.random() * 2 - 1) * 0.9 * motion
+    phi = float(rng.random()) * 2 * math.pi
+    cell = 48
+    ch, cw = (height + cell - 1) // cell, (width + cell - 1) // cell
+    layer = rng.integers(0, 4, (ch, cw))
+    shift = np.array([0.0, 0.4, 0.9, 1.5])[layer] * motion                      # parallax per frame step, by depth layer
+    up = lambda t: t.repeat(cell, 0).repeat(cell, 1)[:height, :width]
+    pdx = np.rint(up(shift * math.cos(phi)) * Q).astype(np.int64)
+    pdy = np.rint(up(shift * math.sin(phi)) * Q).astype(np.int64)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    warps = []
+    for f in range(frames):
+        ct, st = math.cos(f * theta), math.sin(f * theta)
+        # frame pixel (x, y) shows the texture at R(f theta) (p - c - f s) + c (+ pad), then the layer's displacement
+        tx = -ct * (cx + f * sx) - st * (cy + f * sy) + cx + pad
+        ty = st * (cx + f * sx) - ct * (cy + f * sy) + cy + pad
+        warps.append(tuple(int(round(v * Q)) for v in (ct, st, -st, ct, tx, ty)))
+    return base, pad, warps, pdx, pdy, rng
+
+
+def _sequence_frame(base, warp, f, pdx, pdy, height, width, xp=np):
+    """One frame: integer bilinear resampling (16.16 positions, 8-bit weights) of the texture; `xp` is numpy or torch."""
+    H2, W2 = base.shape
+    Q = 1 << 16
+    a, b, c, d, tx, ty = warp
+    if xp is np:
+        xs = np.arange(width, dtype=np.int64)[None, :]
+        ys = np.arange(height, dtype=np.int64)[:, None]
+        clip = np.clip
+    else:
+        xs = xp.arange(width, dtype=xp.int64, device=base.device)[None, :]
+        ys = xp.arange(height, dtype=xp.int64, device=base.device)[:, None]
+        clip = xp.clamp
+    fx = clip(a * xs + b * ys + tx - f * pdx, 0, (W2 - 2) * Q)
+    fy = clip(c * xs + d * ys + ty - f * pdy, 0, (H2 - 2) * Q)
+    x0, y0 = fx >> 16, fy >> 16
+    wx, wy = (fx & (Q - 1)) >> 8, (fy & (Q - 1)) >> 8
+    top = base[y0, x0] * (256 - wx) + base[y0, x0 + 1] * wx
+    bot = base[y0 + 1, x0] * (256 - wx) + base[y0 + 1, x0 + 1] * wx
+    return (top * (256 - wy) + bot * wy + (1 << 15)) >> 16
+
+
+def sequences_numpy(seed, tracks, frames, width, height, motion=1.0):
+    """Short video sequences for the map loop: every track is one textured scene (the texture recipe of frames_torch_hard)
+    seen under a smoothly advancing camera motion -- per frame step an in-plane rotation of up to 0.12 degrees, a shift of up
+    to 0.9 px and a parallax of 0 .. 1.5 px along one epipolar direction by depth layer (48-px cells), all times `motion` --
+    resampled bilinearly in integer arithmetic with fresh noise per frame.  The motion per step is small on purpose: the
+    reference's association looks for a map point within 2 px of where the LAST relative pose puts it.
+    Returns uint8 (tracks, frames, H, W, 3); the same bytes on every machine for a given seed."""
+    out = np.empty((tracks, frames, height, width, 3), np.uint8)
+    tint = np.array([-4, 0, 4], np.int64)
+    for t in range(tracks):
+        base, pad, warps, pdx, pdy, rng = _sequence_plan(seed, t, frames, width, height, motion)
+        bi = np.rint(base).astype(np.int64)
+        for f in range(frames):
+            img = _sequence_frame(bi, warps[f], f, pdx, pdy, height, width)
+            noise = rng.integers(-6, 7, (height, width, 3))
+            out[t, f] = np.clip(img[:, :, None] + noise + tint, 0, 255).astype(np.uint8)
+    return out
+
+
+def sequences_torch(seed, tracks, frames, width, height, device, motion=1.0):
+    """sequences_numpy's construction on `device` (same textures and warps; the per-frame noise comes from the device's
+    generator, so the bytes differ from the numpy form).  Returns uint8 (tracks, frames, H, W, 3)."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed) ^ 0x5E9)
+    out = torch.empty((tracks, frames, height, width, 3), dtype=torch.uint8, device=device)
+    tint = torch.tensor([-4, 0, 4], device=device)
+    for t in range(tracks):
+        base, pad, warps, pdx, pdy, _ = _sequence_plan(seed, t, frames, width, height, motion)
+        bi = torch.from_numpy(np.rint(base).astype(np.int64)).to(device)
+        dx, dy = torch.from_numpy(pdx).to(device), torch.from_numpy(pdy).to(device)
+        for f in range(frames):
+            img = _sequence_frame(bi, warps[f], f, dx, dy, height, width, xp=torch)
+            noise = torch.randint(-6, 7, (height, width, 3), generator=g, device=device)
+            out[t, f] = torch.clamp(img[:, :, None] + noise + tint, 0, 255).to(torch.uint8)
+    return out
