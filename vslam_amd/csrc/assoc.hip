@@ -225,12 +225,10 @@ int vs_launch_associate(vslam_ctx *ctx, const float *map_points, const int32_t *
         const size_t words = (size_t)((kp_stride + 31) / 32);
         const size_t lds = sizeof(uint32_t) * (((words + 1) & ~(size_t)1) + (size_t)kp_stride);
         // above 64 KB (kp_stride > 15872; 67584 B at VSLAM_MAX_KP) the launch needs the opt-in; gfx950 has 160 KB per workgroup
-        if (lds > 64 * 1024 && !ctx->attr_done["assoc.resolve"]) {
+        if (lds > 64 * 1024) {
             constexpr size_t kMaxWords = (VSLAM_MAX_KP + 31) / 32;
             constexpr size_t kMaxLds = sizeof(uint32_t) * (((kMaxWords + 1) & ~(size_t)1) + (size_t)VSLAM_MAX_KP);
-            VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(assoc_resolve_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
-            ctx->attr_done["assoc.resolve"] = true;
+            if ((rc = vs_allow_dynamic_lds(ctx, assoc_resolve_kernel, "assoc.resolve", kMaxLds))) return rc;
         }
         assoc_resolve_kernel<<<batch, kRT, lds, ctx->stream>>>(n_map, map_stride, n_kp, kp_stride, cand, cand_cnt, map_point_ids,
                                                               claim);

@@ -129,6 +129,19 @@ struct VsStreamScope {
 
 static inline int vs_div_up(int a, int b) { return (a + b - 1) / b; }
 
+// Let `kernel` be launched with up to `bytes` of dynamic LDS; beyond the default limit a launch fails without this.  The
+// attribute is per device, so it is set once per context and remembered under `key`.  When a launch needs it (the limit
+// differs with the kernel's static LDS) is the caller's condition.
+template <typename K>
+int vs_allow_dynamic_lds(vslam_ctx *ctx, K kernel, const char *key, size_t bytes) {
+    bool &done = ctx->attr_done[key];
+    if (!done) {
+        VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done = true;
+    }
+    return VSLAM_OK;
+}
+
 // A/B switches (slower kernel variants, stream arrangements, tile shapes measured and not chosen) exist only in the
 // EXPERIMENTS build of the library (-DVSLAM_EXPERIMENTS -> libvslam_amd_exp.so, which tools/ab_*.py and the variant tests load
 // through VSLAM_AMD_LIB / capi.load_library): the default build reads no environment variable and carries one kernel per stage.

@@ -292,11 +292,8 @@ int vs_launch_kdtree_build(vslam_ctx *ctx, const float *xy, const int32_t *n, in
     VsProfScope ps(ctx, "kdtree_build_kernel");
 #define VS_KD_LAUNCH(T, M, I)                                                                                               \
     do {                                                                                                                    \
-        if (!ctx->attr_done["kdtree_build" #T "_" #M #I]) {                                                                 \
-            VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kdtree_build_kernel<T, M, I>),                   \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));                 \
-            ctx->attr_done["kdtree_build" #T "_" #M #I] = true;                                                             \
-        }                                                                                                                   \
+        if (int arc = vs_allow_dynamic_lds(ctx, (kdtree_build_kernel<T, M, I>), "kdtree_build" #T "_" #M #I, 160 * 1024 - 512)) \
+            return arc;                                                                                                     \
         kdtree_build_kernel<T, M, I><<<batch, T, lds, ctx->stream>>>(xy, n, kp_stride, nodes);                              \
     } while (0)
 #ifdef VSLAM_EXPERIMENTS

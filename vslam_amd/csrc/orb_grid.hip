@@ -1315,10 +1315,8 @@ int launch_retain(vslam_ctx *ctx, const Geom &G, int n_lists, int max_len, uint3
     if (max_len + 1 > kTier2) {
         auto k = retain_best_kernel<S, kTier3, kTier2, 1, false>;
         const char *key = S::kBytes == 4 ? "orb_grid.retain3s" : "orb_grid.retain3r";
-        if (kTier3 * per > 64 * 1024 && !ctx->attr_done[key]) {
-            VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, kTier3 * per));
-            ctx->attr_done[key] = true;
-        }
+        if (kTier3 * per > 64 * 1024)
+            if (int rc = vs_allow_dynamic_lds(ctx, k, key, kTier3 * per)) return rc;
         k<<<n_lists, 64, (size_t)kTier3 * per, st>>>(G, n_lists, ent, resp, cnt_in, cnt_out, flags, nullptr, nullptr, nullptr);
     }
     if (max_len + 1 > kTier3)
@@ -1427,11 +1425,7 @@ int vs_launch_extract_grid(vslam_ctx *ctx, uint8_t *bgr, int frames, int w, int 
     }
     {
         VsProfScope ps(ctx, "fast_collect_kernel");
-        if (fast_lds > 64 * 1024 && !ctx->attr_done["orb_grid.fast"]) {
-            VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(fast_collect_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            ctx->attr_done["orb_grid.fast"] = true;
-        }
+        if (fast_lds > 64 * 1024 && (rc = vs_allow_dynamic_lds(ctx, fast_collect_kernel, "orb_grid.fast", 150 * 1024))) return rc;
         fast_collect_kernel<<<units * G.nlv, 256, fast_lds, st>>>(G, units, fast_lds, gray, cpyr, ent, cnt0, c1_20);
         grid_decide_kernel<<<vs_div_up(units, 256), 256, 0, st>>>(G, units, c1_20, flags);
     }

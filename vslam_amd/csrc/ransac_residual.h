@@ -1,0 +1,72 @@
+// The residual of one correspondence under F as the reference evaluates it: what ransac_count.hip and ransac_select.hip
+// share.  Device helpers only; no kernel lives here.
+//
+// Replaces the per-correspondence arithmetic of RansacFilter::compute_fundamental_residual (the reference's
+// src/RansacFilter.cpp:119-126).
+//
+// Numerics: bit-exact.  Same IEEE operations in the same order as the reference's OpenCV expressions (no FMA contraction:
+// -ffp-contract=off; explicit fma() only where the product of two floats is exact in double).  Every inlier decision
+// (e <= threshold) and every residual sum the accept rule sees is made from these values.
+#pragma once
+
+#include "ctx.h"
+
+namespace vs_ransac {
+
+// e for one correspondence under F, exactly as RansacFilter.cpp:119-126 evaluates it through
+// OpenCV: F*x1 in float (left to right), F.t()*x2 in double with one rounding, the row reduce
+// as (r0 + r1) + r2, and n*n / a*a + b*b + c*c + d*d with C++ precedence.
+struct ResidualF {
+    float f[9];
+    double ft[6];   // F[0],F[3],F[6], F[1],F[4],F[7] as doubles
+};
+__device__ __forceinline__ void residual_prepare(ResidualF &R) {
+    R.ft[0] = (double)R.f[0];
+    R.ft[1] = (double)R.f[3];
+    R.ft[2] = (double)R.f[6];
+    R.ft[3] = (double)R.f[1];
+    R.ft[4] = (double)R.f[4];
+    R.ft[5] = (double)R.f[7];
+}
+__device__ __forceinline__ float residual_e(const ResidualF &R, const float4 c, const double dx2, const double dy2) {
+    const float x1 = c.x, y1 = c.y, x2 = c.z, y2 = c.w;
+    const float a0 = R.f[0] * x1 + R.f[1] * y1 + R.f[2];
+    const float a1 = R.f[3] * x1 + R.f[4] * y1 + R.f[5];
+    const float a2 = R.f[6] * x1 + R.f[7] * y1 + R.f[8];
+    // products of two floats are exact in double: fma(a,b,c) == a*b + c rounded once
+    const float t0 = (float)(__builtin_fma(R.ft[1], dy2, R.ft[0] * dx2) + R.ft[2]);
+    const float t1 = (float)(__builtin_fma(R.ft[4], dy2, R.ft[3] * dx2) + R.ft[5]);
+    const float n = (x2 * a0 + y2 * a1) + a2;
+    const float q = (n * n) / (a0 * a0);
+    return ((q + a1 * a1) + t0 * t0) + t1 * t1;
+}
+
+// Two correspondences at once: the float multiplies and adds become v_pk_mul_f32 / v_pk_add_f32 (IEEE, same
+// roundings as the scalar forms), which halves the float instruction count of the hot loop; the double
+// part (F.t()*x2) and the division stay per element.  Lane .x is the lower correspondence index.
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2f residual_e2(const ResidualF &R, const v2f x1, const v2f y1, const v2f x2, const v2f y2,
+                                           const double2 da, const double2 db) {
+    const v2f a0 = (R.f[0] * x1 + R.f[1] * y1) + R.f[2];
+    const v2f a1 = (R.f[3] * x1 + R.f[4] * y1) + R.f[5];
+    const v2f a2 = (R.f[6] * x1 + R.f[7] * y1) + R.f[8];
+    v2f t0, t1;
+    t0.x = (float)(__builtin_fma(R.ft[1], da.y, R.ft[0] * da.x) + R.ft[2]);
+    t0.y = (float)(__builtin_fma(R.ft[1], db.y, R.ft[0] * db.x) + R.ft[2]);
+    t1.x = (float)(__builtin_fma(R.ft[4], da.y, R.ft[3] * da.x) + R.ft[5]);
+    t1.y = (float)(__builtin_fma(R.ft[4], db.y, R.ft[3] * db.x) + R.ft[5]);
+    const v2f n = (x2 * a0 + y2 * a1) + a2;
+    const v2f nn = n * n, dd = a0 * a0;
+    v2f q;
+    q.x = nn.x / dd.x;
+    q.y = nn.y / dd.y;
+    return ((q + a1 * a1) + t0 * t0) + t1 * t1;
+}
+
+}  // namespace vs_ransac
+
+// The counts-first scoring up to and including ransac_count_kernel (ransac_count.hip), called by vs_launch_ransac_evaluate
+// (ransac_select.hip) and by nobody else.  approx: 2 floats per hypothesis, the cheap sum and its error bound.
+int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, const int32_t *pairs, const int32_t *m,
+                           const float *hypF, int batch, int kp_stride, int hyp, float threshold, int32_t *hyp_count,
+                           float *hyp_sum, float *approx);

@@ -937,11 +937,7 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
         for (int k = disc.n; k < disc.n + 3 && k < kDiscMax + 3; k++) disc.e[k] = disc.n ? disc.e[0] : 0;
 #define VS_SELECT_LAUNCH(EPT, PASS, KEYS, COUNTS)                                                                          \
     do {                                                                                                                   \
-        if (!ctx->attr_done["corner_select" #EPT]) {                                                                       \
-            VS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(corner_select_kernel<EPT>),                     \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));                     \
-            ctx->attr_done["corner_select" #EPT] = true;                                                                   \
-        }                                                                                                                  \
+        if ((rc = vs_allow_dynamic_lds(ctx, corner_select_kernel<EPT>, "corner_select" #EPT, 128 * 1024))) return rc;      \
         if (PASS == 2)                                                                                                     \
             corner_select_kernel<EPT><<<pool.slots, kST, lds, ctx->stream>>>(                                              \
                 pool.eig, nullptr, c.need, 2, w, h, pool.state, pool.keys, pool.counts, pool.key_cap, max_corners, md, md2, \
