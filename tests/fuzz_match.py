@@ -1,7 +1,7 @@
 """Randomised parity of the matcher: ragged batches of random descriptor sets with planted copies, near copies, repeated
 train rows (distance ties: the lower index must win), all-zero / all-one / complementary rows, sizes from 0 to a few
 hundred rows, every workgroup shape and matrix-core form; indices, distances and the ratio-test survivors must equal the
-oracle's (src/Frame.cpp:83-94).
+oracle's (src/Frame.cpp:83-94), and the integer definitions of tests/ref_int.py, which were not written from the oracle.
 
 `python tests/fuzz_match.py SEED SECONDS` runs it for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
 import sys
@@ -10,10 +10,13 @@ import time
 import numpy as np
 import torch
 
+import ref_int
 
-def run(ctx, o, seed, cases=None, seconds=None, variants=True):
+
+def run(ctx, o, seed, cases=None, seconds=None, variants=True, stats=None):
     """variants: draw a workgroup shape and a matrix-core form per case (a context of the EXPERIMENTS build; the product
     library carries one matcher and refuses the options)."""
+    stats = {} if stats is None else stats
     rng = np.random.default_rng(seed)
     t0, done = time.time(), 0
     while (cases is None or done < cases) and (seconds is None or time.time() - t0 < seconds):
@@ -76,6 +79,11 @@ def run(ctx, o, seed, cases=None, seconds=None, variants=True):
                 assert rc == 0 and m[b] == len(ref) and np.array_equal(pairs[b, :m[b]], ref), ("pairs", done, b)
             else:
                 assert m[b] == 0, ("degenerate", done, b, len(a), len(t))
+            try:
+                held = ref_int.hold_match(a, t, knn=knn[b, :len(a)] if len(t) >= 2 else None, pairs=pairs[b, :m[b]])
+            except AssertionError as e:
+                raise AssertionError(("ref_int", done, b, len(a), len(t)) + e.args)
+            stats["queries"] = stats.get("queries", 0) + held
         done += 1
         if seconds is not None and done % 200 == 0:
             print(f"fuzz_match: {done} cases ok, {time.time() - t0:.0f} s", flush=True)

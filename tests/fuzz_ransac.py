@@ -2,7 +2,9 @@
 points, small and large match counts, thresholds from 1e-6 to 1e6 — per-hypothesis F, counts, sums, winner, mask and
 final F must equal the oracle's bit for bit.  Extreme scales push the Jacobi rotation out of the range where the
 short f64 sqrt / division sequences apply and the convergence test into its tie branch, so both alternatives of
-every wave-uniform branch get exercised.
+every wave-uniform branch get exercised.  Every case is also held to the float64 definitions of tests/ref64.py (hold_ransac,
+written from src/RansacFilter.cpp and not from the oracle); the inputs are degenerate by design, so what ref64 marks
+undecided keeps only the oracle comparison and is counted in `stats`.
 
 `python tests/fuzz_ransac.py SEED SECONDS` runs for a wall-clock budget; tests/test_gpu_fuzz.py runs a fixed slice."""
 import sys
@@ -11,14 +13,17 @@ import time
 import numpy as np
 import torch
 
+import ref64
+
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def run(ctx, o, seed, cases=None, seconds=None):
+def run(ctx, o, seed, cases=None, seconds=None, stats=None):
     """Cases alternate between the two scoring paths (default: sums of the maximum-count hypotheses only;
     VSLAM_OPT_RANSAC_ALL_SUMS: every sum)."""
+    stats = {} if stats is None else stats
     rng = np.random.default_rng(seed)
     t0, done = time.time(), 0
     while (cases is None or done < cases) and (seconds is None or time.time() - t0 < seconds):
@@ -73,6 +78,12 @@ def run(ctx, o, seed, cases=None, seconds=None):
                 assert out["best"][b, 1] == ref["count"], ("best count",) + tag
                 assert np.array_equal(bits(out["F"][b]), bits(ref["F"])), ("F",) + tag
                 assert np.array_equal(out["mask"][b, :n], ref["mask"]), ("mask",) + tag
+            try:
+                st = ref64.hold_ransac(xy1[b], xy2[b], pairs[b, :n], sets[b], thr, {k: v[b] for k, v in out.items()},
+                                       "all" if all_sums else "ties")
+            except AssertionError as e:
+                raise AssertionError(("ref64",) + tag + e.args)
+            ref64.add_ransac_stats(stats, st)
         done += 1
         if seconds is not None and done % 200 == 0:   # a long run says so as it goes
             print("fuzz_ransac: %d cases ok" % done, flush=True)

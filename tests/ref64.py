@@ -21,6 +21,33 @@ constant times the conditioning of the step:
                                                               4 x 4 DLT system; for exact projections s4 ~ 0 and this is s1/s3.
   reprojected point / projected map point  per coordinate  C_PROJ * EPS * |value| (one rounding of a double dot product
                                                               and one f32 division), plus the double sum's own rounding.
+
+RANSAC (src/RansacFilter.cpp:36-140) is held the same way, the integer parts by tests/ref_int.py:
+
+  fundamental_8pt       src/RansacFilter.cpp:69-103
+  residuals             src/RansacFilter.cpp:105-140
+  hold_ransac           the two above plus the accept rule of :44-66, on one pair's device (or oracle) outputs
+
+  F            Frobenius, either sign   C_F * EPS * (1 + kappa) + the float64 solve's own error.  kappa combines the
+                                        conditioning of the null vector, taken on the column-scaled 8 x 9 system
+                                        (|D v|_1 / s8: see fundamental_8pt), with the gap of the 3 x 3 rank-2 step.
+                                        Decided when the bound is below F_LIMIT = 1e-2: F has unit norm up to the dropped
+                                        singular value, so that separates F from its transpose, a permuted row or a wrong
+                                        rank-2 step.
+  residual e   absolute                 carried through F x1, F^T x2, n, the quotient n^2 / a0^2 and the three squares:
+                                        C_DOT * EPS * (absolute-value sum) per dot product, C_OPS * EPS * (value) per
+                                        quotient / square / sum.
+Calibration (the oracle and the device are bit-identical, so a ratio seen on one is the other's).  Largest error / bound:
+                                         8-point solve (C_F = 8)   residual sum (C_DOT = 3, C_OPS = 4)
+  14 regular pairs of tests/test_oracle_ransac_ref.py     0.118                 0.128     asserted there: <= 1/4, > 0.001
+  its degenerate pairs (coordinates x 1e-9 among them)    0.024                 0.124     printed; <= 1 asserted by the hold
+  the other inputs of tests/test_gpu_ransac.py            0.140                 0.139
+  fixed fuzz slice (tests/test_gpu_fuzz.py, 400 cases)    0.163                 0.143
+  soak and hard regime, every fourth pair (test_gpu_soak) 0.104                 0.154
+so the margin that governs is 6.1x for C_F and 6.5x for the residual constants (4x is the least allowed).  On the regular
+pairs 86 .. 100 % of a pair's solves are decided (noisy integer points 96 .. 100 %, exact sub-pixel points 86 .. 91 %; 78 % of
+all solves have a bound below 1e-3, where F is told from its transpose one solve at a time), 0 .. 0.07 % of a pair's
+evaluations are undecided, and no decided evaluation of any hypothesis disagrees with the oracle's mask.
 A decision (trace sign, t_z sign, re <= thresholdSq, 0 <= x < W, d^2 < r^2) is *decided* when the quantity lies further
 from its boundary than the error bound carried to it; only decided outcomes are asserted.  The constants were calibrated
 once (tests/test_oracle_pose.py, tests/test_oracle_assoc.py report the largest observed error / bound ratio) and carry a
@@ -366,3 +393,282 @@ def hold_association(map_points, c2, img_w, img_h, nodes, kp_xy, kp_desc, obs_of
     assert np.array_equal(np.asarray(claim), r["claim"]), ("claims", np.nonzero(np.asarray(claim) != r["claim"])[0][:10])
     assert np.array_equal(np.asarray(ids_out), r["ids"]), "map_point_ids"
     return True
+
+
+# =============================================================================================== RANSAC (RansacFilter.cpp)
+# See the module docstring's RANSAC section for the bounds and their calibration.
+C_F = 8.0             # 8-point solve: Frobenius bound C_F * EPS * (1 + kappa)
+F_LIMIT = 1e-2        # a solve is decided when its bound is below this
+F_TIGHT = 1e-3        # ... and can tell F from its transpose when below this (reported, see fundamental_check)
+C_DOT = 3.0           # residual: one f32 dot product of three terms, times its absolute-value sum
+C_OPS = 4.0           # residual: the quotient, a square, the four-term sum, each times its value
+_TINY = 2.0 ** -126   # smallest normal f32: below it a product has lost relative accuracy
+_HUGE = 2.0 ** 120    # above it a square overflows f32
+
+
+def fundamental_8pt(p1_set, p2_set):
+    """src/RansacFilter.cpp:69-103 for a batch of samples p1_set, p2_set (H, 8, 2): the 8 x 9 system of :81-89 with its
+    entries rounded to f32 as the reference stores them, its SVD (:94), F0 = V_t.row(8) (:95), the 3 x 3 SVD (:98), the third
+    singular value set to 0 (:99), F = U diag(D) V_t (:101).  Returns a dict:
+      F (H, 3, 3); s9 (H, 8) and s3 (H, 3) the singular values of both steps; sc (H, 8) those of the column-scaled system;
+      kappa = (1 + |D v|_1 / s9_8) * (1 + 2 * s3_3 / (s3_2 - s3_3)) - 1: the null vector v taken on the column-scaled
+              system (D = the column norms of A; see the comment in the code), then the gap of the 3 x 3 step that separates
+              the dropped singular direction from the kept ones;
+      tol = C_F * EPS * (1 + kappa) + this reference's own float64 error, Frobenius, on min(|F - F'|, |F + F'|) (the sign of
+            a null vector is free);
+      decided = tol < F_LIMIT.  A zero column, a repeated or collinear sample, any rank below 8 give kappa = inf."""
+    p1 = _f64(p1_set).reshape(-1, 8, 2); p2 = _f64(p2_set).reshape(-1, 8, 2)
+    H = len(p1)
+    if H == 0:
+        z = np.zeros(0)
+        return dict(F=np.zeros((0, 3, 3)), s9=np.zeros((0, 8)), s3=np.zeros((0, 3)), sc=np.zeros((0, 8)), kappa=z, tol=z,
+                    decided=z.astype(bool))
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)
+    u1, v1, u2, v2 = p1[..., 0], p1[..., 1], p2[..., 0], p2[..., 1]
+    one = np.ones_like(u1)
+    with np.errstate(all="ignore"):
+        A = np.stack([f32(u2 * u1), f32(u2 * v1), u2, f32(v2 * u1), f32(v2 * v1), v2, u1, v1, one], axis=2)   # :81-89
+        finite = np.isfinite(A).all(axis=(1, 2))
+        A = np.where(finite[:, None, None], A, 0.0)
+        # :94-95.  The null vector is taken through the column-scaled system A = B D, D = diag(column norms): LAPACK's error is
+        # 2^-52 times the condition of the matrix it is given, and B's is thousands of times smaller than A's (pixel
+        # coordinates: columns of 1e6 beside a column of ones).  B w = 0  <=>  A (D^-1 w) = 0.
+        s9 = np.linalg.svd(A, compute_uv=False)
+        d = np.linalg.norm(A, axis=1)                                 # (H, 9) column norms
+        s8 = s9[:, 7] - 2.0 ** -48 * s9[:, 0]        # LAPACK knows s8 to 2^-52 s1 only: the lower end of what it can be
+        ok = finite & (d > 0).all(1) & (s8 > 0)
+        dinv = 1.0 / np.where(d > 0, d, 1.0)
+        _, sc, Wt9 = np.linalg.svd(A * dinv[:, None, :])              # FULL_UV
+        v = Wt9[:, 8, :] * dinv
+        nv = np.linalg.norm(v, axis=1)
+        v = v / nv[:, None]
+        F0 = v.reshape(H, 3, 3)
+        U, s3, Wt = np.linalg.svd(F0)                                 # :98
+        F = (U[:, :, :2] * s3[:, None, :2]) @ Wt[:, :2, :]            # :99-101
+        # What an f32 solve can differ by: a rotation of two rows perturbs every entry relative to its own column, dA = E D
+        # with |E| ~ EPS, so to first order |dv| = |A^+ E D v| <= |E| |D v|_1 / s8(A): the 1-norm of the SCALED null vector
+        # over the smallest singular value.
+        w1 = np.abs(v * d).sum(1)                                     # |D v|_1
+        k_null = np.where(ok, w1 / np.where(s8 > 0, s8, 1.0), np.inf)
+        k_null = np.where(sc[:, 7] > 64 * EPS * sc[:, 0], k_null, np.inf)      # rank below 8 to working precision
+        # and this reference's own error: 2^-52 cond(B), carried back through D^-1 (largest 1 / d over |D^-1 w|)
+        own = 16 * 2.0 ** -52 * (dinv.max(1) / nv) * sc[:, 0] / np.where(sc[:, 7] > 0, sc[:, 7], 1.0)
+        gap = s3[:, 1] - s3[:, 2]
+        k_3 = np.where(gap > 0, s3[:, 2] / np.where(gap > 0, gap, 1.0), np.inf)
+        kappa = (1.0 + k_null) * (1.0 + 2.0 * k_3) - 1.0
+        tol = C_F * EPS * (1.0 + kappa) + own * (1.0 + 2.0 * k_3)
+    tol = np.where(np.isfinite(tol), tol, np.inf)
+    return dict(F=F, s9=s9, s3=s3, sc=sc, kappa=kappa, tol=tol, decided=tol < F_LIMIT)
+
+
+def fundamental_error(F_dev, ref):
+    """min(|F - F_dev|, |F + F_dev|), Frobenius, per hypothesis; inf where F_dev is not finite."""
+    Fd = _f64(F_dev).reshape(-1, 3, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = np.minimum(np.linalg.norm((Fd - ref["F"]).reshape(-1, 9), axis=1), np.linalg.norm((Fd + ref["F"]).reshape(-1, 9), axis=1))
+    return np.where(np.isfinite(e), e, np.inf)
+
+
+def fundamental_check(xy1, xy2, pairs, sets, hypF):
+    """Assert every decided solve of one pair: hypF (H, 9) within its bound of fundamental_8pt on the sampled matches.
+    Returns (decided, undecided, worst error / bound ratio, tight) -- tight = the decided solves whose bound is below
+    F_TIGHT = 1e-3: with pixel coordinates |F - F^T| is about 1e-3 of |F|, so these are the solves that can tell F from its
+    transpose one by one (the others still tell a wrong rank-2 step or a permuted row, which change F by O(1))."""
+    pairs = np.asarray(pairs).reshape(-1, 2); sets = np.asarray(sets).reshape(-1, 8)
+    ref = fundamental_8pt(np.asarray(xy1, np.float32).reshape(-1, 2)[pairs[sets, 0]],
+                          np.asarray(xy2, np.float32).reshape(-1, 2)[pairs[sets, 1]])
+    hypF = np.asarray(hypF, np.float32).reshape(len(sets), 9)
+    err = fundamental_error(hypF, ref)
+    dec = ref["decided"]
+    if not dec.any():
+        return 0, int(len(sets)), 0.0, 0
+    ratio = err[dec] / ref["tol"][dec]
+    h = int(np.nonzero(dec)[0][ratio.argmax()])
+    assert ratio.max() <= 1.0, ("8-point solve", h, float(err[h]), float(ref["tol"][h]), hypF[h], ref["F"][h].reshape(9))
+    return int(dec.sum()), int((~dec).sum()), float(ratio.max()), int((ref["tol"] < F_TIGHT).sum())
+
+
+def residuals(F, p1, p2, pairs, thr, chunk=1 << 21, keep=None):
+    """src/RansacFilter.cpp:105-140 in float64 from the f32 inputs, for a batch of hypotheses F (H, 9) over the matches
+    pairs (N, 2) into p1, p2:  a = F x1, c = F^T x2 (:119-120), n = x2 . a (:122-123),
+        e = n^2 / a0^2 + a1^2 + c0^2 + c1^2      exactly as the operators of :126 bind (NOT Sampson's n^2 / (a0^2 + ...)),
+    inlier when e <= thr (:130), sum over all matches (:138).  Per evaluation the error an f32 evaluation can have is carried
+    to first order: da_i = C_DOT EPS (|F_i0 x| + |F_i1 y| + |F_i2|), likewise dc_i; dn = |x2| da0 + |y2| da1 + da2 +
+    C_DOT EPS (|x2 a0| + |y2 a1| + |a2|); the quotient between (|n| -+ dn)^2 / (|a0| +- da0)^2 plus C_OPS EPS of itself; every
+    square 2 |v| dv + dv^2 + C_OPS EPS v^2; the sum C_OPS EPS e.  An evaluation is `valid` when that bound means something:
+    everything finite, da0 <= |a0| / 16, a0^2 a normal f32 and no square near the f32 overflow; it is `decided` when valid
+    and |e - thr| > tol.  Returns a dict, per hypothesis: lo (decided inliers), hi (lo + undecided), n_undecided, sum and
+    sum_tol (float64 sum and its bound; sum_ok where every evaluation is valid, else the two are nan / inf), worst_valid;
+    with keep = a list of hypothesis indices also e / tol / decided / inlier (len(keep), N) for those."""
+    F = _f64(F).reshape(-1, 9)
+    H = len(F)
+    pairs = np.asarray(pairs).reshape(-1, 2)
+    N = len(pairs)
+    q1 = _f64(p1).reshape(-1, 2)[pairs[:, 0]]; q2 = _f64(p2).reshape(-1, 2)[pairs[:, 1]]
+    x1, y1, x2, y2 = q1[:, 0], q1[:, 1], q2[:, 0], q2[:, 1]
+    ax1, ay1, ax2, ay2 = np.abs(x1), np.abs(y1), np.abs(x2), np.abs(y2)
+    thr = float(np.float32(thr))
+    lo = np.zeros(H, np.int64); und = np.zeros(H, np.int64)
+    tot = np.zeros(H); tot_tol = np.zeros(H); sum_ok = np.zeros(H, bool)
+    kept = {}
+    step = max(1, chunk // max(N, 1))
+    for h0 in range(0, H, step):
+        f = F[h0:h0 + step, :, None]                                  # (h, 9, 1)
+        af = np.abs(f)
+        with np.errstate(all="ignore"):
+            a0 = f[:, 0] * x1 + f[:, 1] * y1 + f[:, 2]                # :119
+            a1 = f[:, 3] * x1 + f[:, 4] * y1 + f[:, 5]
+            a2 = f[:, 6] * x1 + f[:, 7] * y1 + f[:, 8]
+            c0 = f[:, 0] * x2 + f[:, 3] * y2 + f[:, 6]                # :120, F.t()
+            c1 = f[:, 1] * x2 + f[:, 4] * y2 + f[:, 7]
+            da0 = C_DOT * EPS * (af[:, 0] * ax1 + af[:, 1] * ay1 + af[:, 2])
+            da1 = C_DOT * EPS * (af[:, 3] * ax1 + af[:, 4] * ay1 + af[:, 5])
+            da2 = C_DOT * EPS * (af[:, 6] * ax1 + af[:, 7] * ay1 + af[:, 8])
+            dc0 = C_DOT * EPS * (af[:, 0] * ax2 + af[:, 3] * ay2 + af[:, 6])
+            dc1 = C_DOT * EPS * (af[:, 1] * ax2 + af[:, 4] * ay2 + af[:, 7])
+            n = x2 * a0 + y2 * a1 + a2                                # :122-123
+            dn = ax2 * da0 + ay2 * da1 + da2 + C_DOT * EPS * (np.abs(x2 * a0) + np.abs(y2 * a1) + np.abs(a2))
+            aa0, an = np.abs(a0), np.abs(n)
+            q = n * n / (a0 * a0)                                     # :126, first term
+            den_lo = np.maximum(aa0 - da0, 0.0) ** 2
+            q_hi = ((an + dn) ** 2 + _TINY) / den_lo
+            q_lo = np.maximum(an - dn, 0.0) ** 2 / (aa0 + da0) ** 2
+            dq = np.maximum(q_hi - q, q - q_lo) + C_OPS * EPS * q_hi
+            sq = a1 * a1 + c0 * c0 + c1 * c1
+            dsq = (2 * np.abs(a1) * da1 + da1 * da1 + 2 * np.abs(c0) * dc0 + dc0 * dc0 + 2 * np.abs(c1) * dc1 + dc1 * dc1 +
+                   C_OPS * EPS * sq + 3 * _TINY)
+            e = q + sq
+            tol = dq + dsq + C_OPS * EPS * (q_hi + sq)
+            valid = (np.isfinite(e) & np.isfinite(tol) & (16 * da0 <= aa0) & (den_lo >= _TINY) &
+                     ((an + dn) < 2.0 ** 60) & (q_hi + sq + tol < _HUGE))
+            decided = valid & (np.abs(e - thr) > tol)
+            inl = e <= thr
+        lo[h0:h0 + step] = (decided & inl).sum(1)
+        und[h0:h0 + step] = (~decided).sum(1)
+        allv = valid.all(1)
+        sum_ok[h0:h0 + step] = allv
+        with np.errstate(all="ignore"):
+            s = np.where(valid, e, 0.0).sum(1)
+            tot[h0:h0 + step] = np.where(allv, s, np.nan)
+            # cv::sum accumulates in double (:138) and is rounded to float once
+            tot_tol[h0:h0 + step] = np.where(allv, np.where(valid, tol, 0.0).sum(1) + EPS * np.abs(s), np.inf)
+        if keep is not None:
+            for k in keep:
+                if h0 <= k < h0 + step:
+                    kept[k] = (e[k - h0], tol[k - h0], decided[k - h0], inl[k - h0])
+    out = dict(lo=lo, hi=lo + und, n_undecided=und, sum=tot, sum_tol=tot_tol, sum_ok=sum_ok, n=N)
+    if keep is not None:
+        for i, name in enumerate(("e", "tol", "decided", "inlier")):
+            out[name] = np.stack([kept[k][i] for k in keep]) if len(keep) else np.zeros((0, N))
+    return out
+
+
+def new_ransac_stats():
+    return dict(solves=0, solves_undecided=0, solves_tight=0, evals=0, evals_undecided=0, pairs=0, pairs_undecided=0, worst_F=0.0,
+                worst_sum=0.0)
+
+
+def add_ransac_stats(total, st):
+    for k, v in st.items():
+        total[k] = max(total.get(k, 0.0), v) if k.startswith("worst") else total.get(k, 0) + v
+    return total
+
+
+def ransac_shares(st):
+    """One line for a test to print: the held / undecided shares and the worst error / bound ratios."""
+    pc = lambda a, b: 100.0 * a / max(a + b, 1)
+    return ("solves held %d (%.1f %%; bound < 1e-3: %d), evaluations undecided %d of %d (%.4f %%), winner checks held %d undecided %d, "
+            "worst ratio F %.4f sum %.4f" % (st["solves"], pc(st["solves"], st["solves_undecided"]), st["solves_tight"], st["evals_undecided"],
+                                             st["evals"] + st["evals_undecided"],
+                                             100.0 - pc(st["evals"], st["evals_undecided"]), st["pairs"],
+                                             st["pairs_undecided"], st["worst_F"], st["worst_sum"]))
+
+
+def hold_ransac(xy1, xy2, pairs, sets, thr, out, mode="all", solve=True):
+    """Hold one pair's RANSAC outputs to fundamental_8pt, residuals and the accept rule of src/RansacFilter.cpp:44-66.
+    pairs (n, 2) are the preliminary matches, sets (H, 8) the sample sets, out the outputs for this pair: hypF (H, 9),
+    hyp_count (H), hyp_sum (H), best (4: winner, count, sum bits, kept), F (9), mask (>= n), matches (>= kept, 2).  mode "all":
+    every hypothesis carries its count and sum; "ties" (the default scoring path): a count may read -1 and a sum NaN / -inf
+    where the hypothesis cannot win.  solve=False skips the comparison of hypF with the 8-point solve (hand-made hypF).
+    Asserts, each stage given the inputs it actually received:
+      * every decided solve: hypF within tol of fundamental_8pt, either sign;
+      * with the device's own hypF through residuals: a carried count in [lo, hi]; a carried finite sum within sum_tol where
+        sum_ok; in "all" mode every count and sum is carried; in "ties" mode a NaN sum only with a -1 count or where the
+        sum is not sum_ok (where a -1 and a -inf are allowed follows from the winner rules below);
+      * the winner: best[1] in its [lo, hi]; no hypothesis has lo above the winner's hi; among the hypotheses decided to tie
+        with it (lo == hi == its count) none has a float64 sum above the winner's by more than the two bounds; F is its hypF;
+        without a winner (-1) no hypothesis has a decided inlier;
+      * the mask equals e <= thr on every decided match of the winner; best[3] and matches are the masked pairs in order.
+    Returns counts (new_ransac_stats): solves held / undecided, evaluations decided / undecided, pairs = 1 when the winner
+    check was held (at most 1 % of the winner's evaluations undecided, one at least allowed; without a winner: no hypothesis
+    has an undecided evaluation), and the largest error / bound ratios."""
+    st = new_ransac_stats()
+    pairs = np.asarray(pairs).reshape(-1, 2)
+    n = len(pairs)
+    sets = np.asarray(sets).reshape(-1, 8)
+    H = len(sets)
+    hypF = np.asarray(out["hypF"], np.float32).reshape(H, 9)
+    cnt = np.asarray(out["hyp_count"]).reshape(H).astype(np.int64)
+    hs = np.asarray(out["hyp_sum"], np.float32).reshape(H).astype(np.float64)
+    best = np.asarray(out["best"]).reshape(4)
+    w = int(best[0])
+    # ---- the solves
+    if solve:
+        st["solves"], st["solves_undecided"], st["worst_F"], st["solves_tight"] = fundamental_check(xy1, xy2, pairs, sets, hypF)
+    # ---- counts and sums, from the device's own hypotheses
+    r = residuals(hypF, xy1, xy2, pairs, thr, keep=[w] if w >= 0 else [])
+    lo, hi = r["lo"], r["hi"]
+    st["evals"], st["evals_undecided"] = int(H * n - r["n_undecided"].sum()), int(r["n_undecided"].sum())
+    carried = cnt >= 0
+    if mode == "all":
+        assert carried.all(), ("a count is missing in all-sums mode", np.nonzero(~carried)[0][:5])
+    bad = np.nonzero(carried & ((cnt < lo) | (cnt > hi)))[0]
+    assert bad.size == 0, ("inlier count", bad[:5], cnt[bad[:5]], lo[bad[:5]], hi[bad[:5]])
+    assert (cnt[~carried] == -1).all(), "a negative count other than -1"
+    fin = np.isfinite(hs)
+    chk = fin & r["sum_ok"] & (carried if mode != "all" else True)
+    with np.errstate(invalid="ignore"):
+        sratio = np.abs(hs[chk] - r["sum"][chk]) / r["sum_tol"][chk]
+    if chk.any():
+        h = int(np.nonzero(chk)[0][sratio.argmax()])
+        assert sratio.max() <= 1.0, ("residual sum", h, float(hs[h]), float(r["sum"][h]), float(r["sum_tol"][h]))
+        st["worst_sum"] = float(sratio.max())
+    if mode == "all":
+        bad = np.nonzero(r["sum_ok"] & (np.abs(r["sum"]) + r["sum_tol"] < _HUGE) & ~fin)[0]
+        assert bad.size == 0, ("a sum is missing in all-sums mode", bad[:5], hs[bad[:5]])
+    # ---- the winner
+    if w < 0:
+        assert (lo == 0).all(), ("no winner, yet a hypothesis has decided inliers", int(lo.argmax()), int(lo.max()))
+        assert best[3] == 0
+        held = bool((hi == 0).all())
+        st["pairs"], st["pairs_undecided"] = int(held), int(not held)
+        return st
+    assert 0 <= w < H
+    assert lo[w] <= int(best[1]) <= hi[w], ("winner's count", w, int(best[1]), int(lo[w]), int(hi[w]))
+    if carried[w]:
+        assert int(best[1]) == cnt[w], ("best count is not the winner's", int(best[1]), int(cnt[w]))
+    # a maximum-count hypothesis as float64 sees it (this also covers every abandoned hypothesis: a -1 with lo above the
+    # winner's hi would be one of these)
+    above = np.nonzero(lo > hi[w])[0]
+    assert above.size == 0, ("a hypothesis has more inliers than the winner", w, int(hi[w]), above[:5], lo[above[:5]])
+    if mode != "all":
+        bad = np.nonzero(np.isnan(hs) & carried & r["sum_ok"])[0]
+        assert bad.size == 0, ("a counted hypothesis without its sum", bad[:5])
+    # among the hypotheses decided to tie with the winner none has the larger sum, whatever the device reports for it
+    # (a finite sum, -inf "pruned", or a -1 count "abandoned on the sum")
+    if r["sum_ok"][w] and lo[w] == hi[w]:
+        tie = (lo == hi) & (lo == lo[w]) & r["sum_ok"]
+        beat = np.nonzero(tie & (r["sum"] - r["sum_tol"] > r["sum"][w] + r["sum_tol"][w]))[0]
+        assert beat.size == 0, ("a tied hypothesis has the larger residual sum", w, float(r["sum"][w]), beat[:5], r["sum"][beat[:5]])
+    assert np.array_equal(np.asarray(out["F"], np.float32).reshape(9).view(np.uint32), hypF[w].view(np.uint32)), "F is not the winner's"
+    # ---- mask and filtered matches
+    mask = np.asarray(out["mask"]).reshape(-1)[:n] != 0
+    d = r["decided"][0]
+    bad = np.nonzero(d & (mask != r["inlier"][0]))[0]
+    assert bad.size == 0, ("inlier mask", w, bad[:5], r["e"][0][bad[:5]], r["tol"][0][bad[:5]])
+    k = int(mask.sum())
+    assert int(best[3]) == k, ("kept matches", int(best[3]), k)
+    assert np.array_equal(np.asarray(out["matches"]).reshape(-1, 2)[:k], pairs[mask]), "matches are not the masked pairs in order"
+    held = int((~d).sum()) <= max(1, n // 100)
+    st["pairs"], st["pairs_undecided"] = int(held), int(not held)
+    return st

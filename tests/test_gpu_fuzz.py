@@ -12,13 +12,20 @@ def test_extraction_stages_on_random_shapes(ctx, oracle):
 
 def test_matcher_on_random_ragged_batches(ctx, ctx_exp, oracle):
     import fuzz_match
-    assert fuzz_match.run(ctx, oracle, seed=20261006, cases=60, variants=False) == 60      # the product's one matcher
-    assert fuzz_match.run(ctx_exp, oracle, seed=20261007, cases=60, variants=True) == 60   # its variants (experiments build)
+    stats = {}
+    assert fuzz_match.run(ctx, oracle, seed=20261006, cases=60, variants=False, stats=stats) == 60      # the product's one matcher
+    assert fuzz_match.run(ctx_exp, oracle, seed=20261007, cases=60, variants=True, stats=stats) == 60   # its variants (experiments build)
+    print("matcher fuzz: queries held to tests/ref_int.py:", stats)
+    assert stats["queries"] > 5000, stats       # every query of every item, exactly (nothing is undecided in integers)
 
 
 def test_ransac_kernels_on_random_and_degenerate_inputs(ctx, oracle):
     import fuzz_ransac
-    assert fuzz_ransac.run(ctx, oracle, seed=20261005, cases=400) == 400
+    import ref64
+    stats = ref64.new_ransac_stats()
+    assert fuzz_ransac.run(ctx, oracle, seed=20261005, cases=400, stats=stats) == 400
+    print("RANSAC fuzz:", ref64.ransac_shares(stats))
+    assert stats["pairs"] > stats["pairs_undecided"], stats      # most pairs' winner checks are held to tests/ref64.py as well
 
 
 def test_grid_extractor_on_random_shapes_grids_and_content(ctx, oracle):

@@ -1,7 +1,10 @@
-"""HIP match kernel vs the oracle (bit-exact: indices, distances, pair lists)."""
+"""HIP match kernel vs the oracle (bit-exact: indices, distances, pair lists), and vs the integer definitions of tests/ref_int.py
+(written from src/Frame.cpp:83-94, not from the oracle)."""
 import numpy as np
 import pytest
 import torch
+
+import ref_int
 
 from vslam_amd import synth
 
@@ -69,6 +72,7 @@ def test_knn2_and_ratio_bit_exact_ragged_batch(mctx, oracle):
             assert np.array_equal(pairs[b, :m[b]], ref), b
         else:
             assert m[b] == 0      # reference reads m[1] of a 1-row result: undefined; we emit nothing
+        ref_int.hold_match(a, t, knn=knn[b, :len(a)] if len(t) >= 2 else None, pairs=pairs[b, :m[b]])
 
 
 def test_full_size_property_self_match(mctx):
@@ -89,6 +93,8 @@ def test_full_size_property_self_match(mctx):
     assert torch.equal(knn[:, :, 0], inv) and int(knn[:, :, 1].abs().sum()) == 0
     assert torch.all(m == K)
     assert torch.equal(pairs[:, :, 1], inv)
+    for b in range(B):            # and through the definition (about a second of CPU time per item)
+        ref_int.hold_match(d1[b].numpy(), d2[b].numpy(), knn=knn[b].numpy(), pairs=pairs[b, :int(m[b])].numpy())
 
 
 def test_extreme_distances_and_index_range(mctx, oracle):
@@ -118,5 +124,6 @@ def test_extreme_distances_and_index_range(mctx, oracle):
         assert np.array_equal(g[:, 2], i1) and np.array_equal(g[:, 3], e1), b
         ref, _ = oracle.match_knn2_ratio(a, tr)
         assert m[b] == len(ref) and np.array_equal(pairs[b, :m[b]], ref), b
+        ref_int.hold_match(a, tr, knn=knn[b, :len(a)], pairs=pairs[b, :m[b]])
     assert knn[0, 11, 0] == K - 1 and knn[0, 11, 1] == 0 and knn[0, 11, 2] == K - 2 and knn[0, 11, 3] == 1
     assert knn[1, 0, 1] >= 250

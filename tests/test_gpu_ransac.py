@@ -1,8 +1,14 @@
 """HIP RANSAC kernels vs the oracle: sets, per-hypothesis F / count / sum, winner, mask, F —
-all bit-exact (the float outputs are compared as uint32 bit patterns)."""
+all bit-exact (the float outputs are compared as uint32 bit patterns).  Beside every such comparison the same device outputs
+are held to references that were not written from the oracle: tests/ref_int.py (sets, matcher) and tests/ref64.py
+(hold_ransac: 8-point solve, residual, accept rule in float64 with error bounds), both restated from src/RansacFilter.cpp."""
 import numpy as np
 import pytest
 import torch
+
+import ref64
+import ref_int
+from ransac_inputs import batch as _batch
 
 from vslam_amd import synth
 
@@ -31,6 +37,22 @@ def _beaten(ref_count, ref_sum):
     if not finite.size:
         return np.zeros(len(rs), bool)
     return top & (rs < finite.max())
+
+
+def hold(xy1, xy2, pairs, sets, thr, out, b, n, mode, stats, solve=True):
+    """Item b of a batch through ref64.hold_ransac; the counts go into stats."""
+    o = {k: v[b] for k, v in out.items()}
+    return ref64.add_ransac_stats(stats, ref64.hold_ransac(xy1[b], xy2[b], pairs[b, :n], sets[b], thr, o,
+                                                           "all" if mode == "all" else "ties", solve))
+
+
+def assert_caps(stats, pairs_held, tag):
+    """On regular inputs: at most 1 % of the evaluations undecided, at least half of the solves decided, every pair's winner
+    check held; the shares are printed."""
+    print(tag, ref64.ransac_shares(stats))
+    assert stats["evals_undecided"] <= 0.01 * (stats["evals"] + stats["evals_undecided"]), (tag, stats)
+    assert stats["solves"] >= stats["solves_undecided"], (tag, stats)
+    assert stats["pairs"] == pairs_held and stats["pairs_undecided"] == 0, (tag, stats)
 
 
 def check_counts(got_count, ref_count, mode, tag=None, ref_sum=None):
@@ -89,6 +111,7 @@ def test_sets_bit_exact(ctx, oracle, H):
     for b, (n, sd) in enumerate(zip(ms, seeds)):
         if n >= 8:
             assert np.array_equal(got[b], oracle.ransac_sets(sd, n, H)), b
+            ref_int.hold_sets(sd, n, H, got[b])
         else:
             assert not got[b].any()
 
@@ -110,6 +133,7 @@ def test_sets_with_fewer_than_eight_items(ctx, oracle, mi):
         for b, (n, sd) in enumerate(zip(ms, seeds)):
             if n >= mi and mi > 0:
                 assert np.array_equal(got[b], oracle.ransac_sets(sd, n, H, min_items=mi)), (mi, b)
+                ref_int.hold_sets(sd, n, H, got[b], mi)
             else:
                 assert not got[b].any()
             assert not got[b][:, mi:].any()
@@ -159,21 +183,7 @@ def test_sets_rejection_path(ctx, oracle):
     ctx.synchronize()
     for b in range(8):
         assert np.array_equal(got[b], oracle.ransac_sets(seeds[b], ms[b], 8192)), b
-
-
-def _batch(seed0, sizes, K, W, H):
-    B = len(sizes)
-    xy1 = np.zeros((B, K, 2), np.float32); xy2 = np.zeros((B, K, 2), np.float32)
-    pairs = np.zeros((B, K, 2), np.int32); m = np.zeros(B, np.int32)
-    for b, n in enumerate(sizes):
-        p1, p2, _ = synth.two_view_points(seed0 + b, K, W, H, inlier_frac=0.65)
-        xy1[b], xy2[b] = p1, p2
-        rng = np.random.default_rng(seed0 * 7 + b)
-        q = np.sort(rng.permutation(K)[:n])
-        pairs[b, :n, 0] = q
-        pairs[b, :n, 1] = q                       # correspondence i <-> i, as two_view_points builds it
-        m[b] = n
-    return xy1, xy2, pairs, m
+        ref_int.hold_sets(seeds[b], ms[b], 8192, got[b])
 
 
 def test_fundamental_bit_exact(ctx, oracle, sums_mode):
@@ -189,6 +199,7 @@ def test_fundamental_bit_exact(ctx, oracle, sums_mode):
     out = ctx.ransac_fundamental(t(xy1), t(xy2), t(pairs), t(m), t(sets), thr)
     ctx.synchronize()
     out = {k: v.cpu().numpy() for k, v in out.items()}
+    stats = ref64.new_ransac_stats()
     for b, n in enumerate(sizes):
         if n < 8:
             assert out["best"][b, 0] == -1 and out["best"][b, 3] == 0
@@ -205,6 +216,9 @@ def test_fundamental_bit_exact(ctx, oracle, sums_mode):
         keep = pairs[b, :n][ref["mask"].astype(bool)]
         assert out["best"][b, 3] == len(keep)
         assert np.array_equal(out["matches"][b, :len(keep)], keep), b
+        ref_int.hold_sets(int(seeds[b]), n, Hy, sets[b])
+        hold(xy1, xy2, pairs, sets, thr, out, b, n, sums_mode, stats)
+    assert_caps(stats, 5, "fundamental")
 
 
 def test_degenerate_geometry_still_bit_exact(ctx, oracle, sums_mode):
@@ -233,6 +247,8 @@ def test_degenerate_geometry_still_bit_exact(ctx, oracle, sums_mode):
         assert out["best"][b, 0] == ref["winner"], b
         if ref["winner"] >= 0:
             assert np.array_equal(out["mask"][b], ref["mask"]), b
+        st = hold(xy1, xy2, pairs, sets, thr, out, b, K, sums_mode, ref64.new_ransac_stats())   # only what is decided
+        print("degenerate", b, ref64.ransac_shares(st))
 
 
 def test_match_features_pipeline_bit_exact(ctx, oracle, sums_mode):
@@ -255,6 +271,25 @@ def test_match_features_pipeline_bit_exact(ctx, oracle, sums_mode):
                              torch.tensor(n2s, dtype=torch.int32).cuda(), t(seeds.view(np.int32)), Hy, thr)
     ctx.synchronize()
     out = {k: v.cpu().numpy() for k, v in out.items()}
+    # the whole chain by definition: ref_int matcher -> ref_int sets -> the RANSAC stage on exactly those -> ref64.hold_ransac
+    prs = np.zeros((B, K, 2), np.int32); pm = np.zeros(B, np.int32); sets = np.zeros((B, Hy, 8), np.int32)
+    for b in range(B):
+        pr = ref_int.ratio_pairs(d1[b, :n1s[b]], d2[b, :n2s[b]])
+        assert out["prelim_m"][b] == len(pr), b
+        prs[b, :len(pr)] = pr; pm[b] = len(pr)
+        if len(pr) >= 8:
+            sets[b] = ref_int.lemire_sets(int(seeds[b]), len(pr), Hy)
+    stage = ctx.ransac_fundamental(t(xy1), t(xy2), t(prs), t(pm), t(sets), thr)
+    ctx.synchronize()
+    stage = {k: v.cpu().numpy() for k, v in stage.items()}
+    stats = ref64.new_ransac_stats()
+    for b in range(B):
+        if pm[b] >= 8:
+            k = int(stage["best"][b, 3])
+            assert np.array_equal(out["best"][b], stage["best"][b]) and np.array_equal(bits(out["F"][b]), bits(stage["F"][b])), b
+            assert np.array_equal(out["matches"][b, :k], stage["matches"][b, :k]), b
+            hold(xy1, xy2, prs, sets, thr, stage, b, int(pm[b]), sums_mode, stats)
+    assert_caps(stats, int((pm >= 8).sum()), "pipeline")
     for b in range(B):
         ref = oracle.match_features(xy1[b, :n1s[b]], d1[b, :n1s[b]], xy2[b, :n2s[b]], d2[b, :n2s[b]],
                                     int(seeds[b]), Hy, thr)
@@ -275,7 +310,8 @@ def _find(ctx, oracle, xy1, xy2, pairs, m, sets, thr):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _compare(out, ref, b, n, mode):
+def _compare(out, ref, b, n, mode, inp=None, stats=None):
+    """inp = (xy1, xy2, pairs, sets, thr): the item is also held to tests/ref64.py, its counts added to stats."""
     check_counts(out["hyp_count"][b], ref["hyp_count"], mode, b, ref["hyp_sum"])
     check_sums(out["hyp_sum"][b], ref["hyp_count"], ref["hyp_sum"], mode, b, out["hyp_count"][b])
     assert out["best"][b, 0] == ref["winner"], b
@@ -284,12 +320,15 @@ def _compare(out, ref, b, n, mode):
         assert out["best"][b, 2] == int(bits(np.float32(ref["sum"])).reshape(-1)[0]), b
         assert np.array_equal(bits(out["F"][b]), bits(ref["F"])), b
         assert np.array_equal(out["mask"][b, :n], ref["mask"]), b
+    if inp is not None:
+        hold(*inp, out, b, n, mode, stats)
 
 
 def test_counts_first_path_at_scale(ctx, oracle, sums_mode):
     """The shapes the counting kernel is built around: several 256-match sub-blocks per hypothesis, a partial last
     sub-block, hypothesis counts that are not a multiple of a workgroup's 128, thresholds that put many evaluations next
     to the decision boundary, and more matches than the LDS staging holds (4096: coordinates read from memory)."""
+    stats = ref64.new_ransac_stats()
     for K, sizes, Hy, thr in ((2304, [2304, 1500, 1025, 257, 256, 64], 200, 10.0), (2304, [1800, 700], 130, 3.0),
                               (2304, [1200, 2000], 64, 40.0), (16384, [16384, 9000, 4097], 70, 10.0)):
         xy1, xy2, pairs, m = _batch(900 + Hy, sizes, K, 1280, 720)
@@ -297,13 +336,15 @@ def test_counts_first_path_at_scale(ctx, oracle, sums_mode):
         out = _find(ctx, oracle, xy1, xy2, pairs, m, sets, thr)
         for b, n in enumerate(sizes):
             ref = oracle.find_fundamental(xy1[b], xy2[b], pairs[b, :n], sets[b], thr)
-            _compare(out, ref, b, n, sums_mode)
+            _compare(out, ref, b, n, sums_mode, (xy1, xy2, pairs, sets, thr), stats)
+    assert_caps(stats, 13, "counts first")
 
 
 def test_screen_and_rank_edge_shapes(ctx, oracle, sums_mode):
     """Shapes around the edges of the ranking / screening stages in front of the counting kernel: fewer hypotheses than
     pilots (8) or candidates, hypothesis counts around a workgroup's 128, match counts around the screen's 128 and the
     256-match sub-blocks (the ranked arrays are padded to a multiple of 256)."""
+    stats = ref64.new_ransac_stats()
     for Hy, sizes in ((1, [8, 200]), (3, [127, 128, 129]), (7, [255, 256, 257]), (9, [383, 384, 385]),
                       (127, [130, 511]), (129, [64, 512, 513]), (257, [100, 300])):
         K = 520
@@ -312,7 +353,8 @@ def test_screen_and_rank_edge_shapes(ctx, oracle, sums_mode):
         out = _find(ctx, oracle, xy1, xy2, pairs, m, sets, 10.0)
         for b, n in enumerate(sizes):
             ref = oracle.find_fundamental(xy1[b], xy2[b], pairs[b, :n], sets[b], 10.0)
-            _compare(out, ref, b, n, sums_mode)
+            _compare(out, ref, b, n, sums_mode, (xy1, xy2, pairs, sets, 10.0), stats)
+    assert_caps(stats, 18, "edge shapes")
 
 
 def test_many_tied_hypotheses(ctx, oracle, sums_mode):
@@ -328,12 +370,14 @@ def test_many_tied_hypotheses(ctx, oracle, sums_mode):
     sets = np.stack([oracle.ransac_sets(31 + b, int(m[b]), Hy) for b in range(2)])
     out = _find(ctx, oracle, xy1, xy2, pairs, m, sets, thr)
     tied = []
+    stats = ref64.new_ransac_stats()
     for b in range(2):
         n = int(m[b])
         ref = oracle.find_fundamental(xy1[b], xy2[b], pairs[b, :n], sets[b], thr)
         tied.append(int((ref["hyp_count"] == ref["hyp_count"].max()).sum()))
-        _compare(out, ref, b, n, sums_mode)
+        _compare(out, ref, b, n, sums_mode, (xy1, xy2, pairs, sets, thr), stats)
     assert max(tied) >= 192, tied      # the top really is crowded
+    print("many tied (identical frames: degenerate, no cap)", ref64.ransac_shares(stats))
 
 
 def test_sum_rule_on_a_plateau_of_tied_hypotheses(ctx, oracle):
@@ -354,21 +398,24 @@ def test_sum_rule_on_a_plateau_of_tied_hypotheses(ctx, oracle):
     out = _find(ctx, oracle, xy1, xy2, pairs, m, sets, thr)
     fired = 0
     crowded = 0
+    stats = ref64.new_ransac_stats()
     for b in range(B):
         n = int(m[b])
         ref = oracle.find_fundamental(xy1[b], xy2[b], pairs[b, :n], sets[b], thr)
-        _compare(out, ref, b, n, "ties")
+        _compare(out, ref, b, n, "ties", (xy1, xy2, pairs, sets, thr), stats)
         tied = ref["hyp_count"] == ref["hyp_count"].max()
         crowded = max(crowded, int(tied.sum()))
         fired += int((tied & (out["hyp_count"][b] == -1)).sum())
     assert crowded >= 40, crowded     # the top really is a plateau
     assert fired > 0                  # and some of it was abandoned on the sum
+    assert_caps(stats, B, "plateau")
 
 
 def test_threshold_and_scale_outside_certified_range(ctx, oracle, sums_mode):
     """Thresholds / coordinates beyond the range the cheap evaluation's bounds are derived for (thr in [2^-20, 2^20],
     |coordinates| <= 2^20): every evaluation must take the exact sequence and still give the reference's counts."""
     K, Hy = 300, 96
+    stats = ref64.new_ransac_stats()
     for scale, thr in ((1.0, 1e-7), (1.0, 3e6), (4e6, 10.0), (1e-9, 10.0), (1.0, -1.0), (1.0, float("inf"))):
         xy1, xy2, pairs, m = _batch(1200, [300, 77], K, 1280, 720)
         xy1 = (xy1 * np.float32(scale)).astype(np.float32); xy2 = (xy2 * np.float32(scale)).astype(np.float32)
@@ -377,7 +424,8 @@ def test_threshold_and_scale_outside_certified_range(ctx, oracle, sums_mode):
         for b in range(2):
             n = int(m[b])
             ref = oracle.find_fundamental(xy1[b], xy2[b], pairs[b, :n], sets[b], thr)
-            _compare(out, ref, b, n, sums_mode)
+            _compare(out, ref, b, n, sums_mode, (xy1, xy2, pairs, sets, thr), stats)
+    print("threshold / scale (only what is decided is asserted)", ref64.ransac_shares(stats))
 
 
 def test_tiny_denominators_take_the_exact_path(ctx, oracle, sums_mode):
@@ -407,7 +455,10 @@ def test_tiny_denominators_take_the_exact_path(ctx, oracle, sums_mode):
     out = ctx.ransac_evaluate(t(xy1), t(xy2), t(pairs), t(m), t(hypF), thr)
     ctx.synchronize()
     out = {k: v.cpu().numpy() for k, v in out.items()}
+    out["hypF"] = hypF
+    stats = ref64.new_ransac_stats()
     for b, n in enumerate(sizes):
+        hold(xy1, xy2, pairs, sets, thr, out, b, n, sums_mode, stats, solve=False)     # a hand-edited hypF has no solve
         counts = np.zeros(Hy, np.int32); sums = np.zeros(Hy, np.float32)
         best, best_sum, winner = 0, np.float32(0.0), -1
         with np.errstate(all="ignore"):
@@ -423,6 +474,7 @@ def test_tiny_denominators_take_the_exact_path(ctx, oracle, sums_mode):
             assert out["best"][b, 1] == best, b
             mask, _, _ = oracle.residual(xy1[b], xy2[b], pairs[b, :n], hypF[b, winner], thr)
             assert np.array_equal(out["mask"][b, :n], mask), b
+    print("tiny denominators (only what is decided is asserted)", ref64.ransac_shares(stats))
 
 
 def test_mfma_solver_is_opt_in_and_agrees_within_its_stated_tolerance(ctx, oracle):

@@ -4,29 +4,7 @@ import pytest
 from vslam_amd import synth
 
 
-def lemire_sets_python(seed, n, H):
-    """Independent restatement of initialize_sets (src/RansacFilter.cpp:6-34): numpy's MT19937
-    seeded by init_genrand is std::mt19937(seed); the mapping is libstdc++'s Lemire
-    multiply-shift with rejection for a 32-bit engine."""
-    rs = np.random.RandomState(seed)
-    raw = lambda: int(rs.randint(0, 2 ** 32, dtype=np.uint64))   # one raw 32-bit output
-    out = np.zeros((H, 8), dtype=np.int32)
-    for i in range(H):
-        avail = list(range(n))
-        for j in range(8):
-            rng = len(avail)
-            prod = raw() * rng
-            low = prod & 0xFFFFFFFF
-            if low < rng:
-                thr = (2 ** 32 - rng) % rng
-                while low < thr:
-                    prod = raw() * rng
-                    low = prod & 0xFFFFFFFF
-            r = prod >> 32
-            out[i, j] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return out
+from ref_int import lemire_sets as lemire_sets_python      # the independent restatement of initialize_sets lives there
 
 
 def test_mt19937_known_answer():
