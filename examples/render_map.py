@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""A video of the map growing, without a window: the synthetic sequences of examples/track_sequences.py are extracted and
+matched once on the device, then the map is advanced one frame at a time (vslam_map_step) and after EVERY step every track's
+map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
+binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
+
+    python examples/render_map.py [output directory]
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vslam_amd import Context, capi, synth  # noqa: E402
+
+
+def write_ppm(path, bgr):
+    """bgr: (H, W, 3) uint8 numpy, written as a binary P6 (which is RGB)."""
+    h, w, _ = bgr.shape
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (w, h))
+        f.write(np.ascontiguousarray(bgr[..., ::-1]).tobytes())
+
+
+def main():
+    out_dir = sys.argv[1] if len(sys.argv) > 1 else "render_map_out"
+    os.makedirs(out_dir, exist_ok=True)
+    tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
+    W, H = 640, 480                                              # of the view
+    dev = torch.device("cuda", 0)
+    ctx = Context(0)
+    cos_a, sin_a = synth.keypoint_rotation()
+    K = np.array([[525.0, 0, width // 2], [0, 525.0, height // 2], [0, 0, 1]], np.float32)   # src/vslam.cpp:32
+    bgr = synth.sequences_torch(7, tracks, frames, width, height, dev)
+    seeds = torch.arange(tracks * (frames - 1), dtype=torch.int32, device=dev).reshape(tracks, frames - 1).contiguous()
+    pmap = capi.PointMap(ctx, tracks, frames, max_corners, map_capacity=frames * max_corners, obs_capacity=4 * frames * max_corners)
+    # features and matches of every frame and consecutive pair, once (this also runs the whole loop; the map is then rebuilt
+    # step by step below so that it can be looked at after every step)
+    out = ctx.track_sequences(pmap, bgr, max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
+    ctx.synchronize()
+    done = pmap.view()
+    pts = np.concatenate([done["points"][t, :done["sizes"][t], :3] for t in range(tracks)]).astype(np.float64)
+    med = np.median(pts, axis=0)
+    spread = float(np.median(np.abs(pts - med))) + 1.0
+    eye = -2.0 * spread * med / (np.linalg.norm(med) + 1e-9) + np.array([0.4 * spread, -0.6 * spread, 0.0])
+    view = capi.View.look_at(eye, med, (0, -1, 0), W, H, fu=0.6 * W, fv=0.6 * W, z_near=0.05, z_far=1e6, point_size=3)
+
+    def per_frame(a, f):
+        return a.view(tracks, frames, *a.shape[1:])[:, f].contiguous()
+
+    def per_pair(a, f):
+        full = torch.cat([a, torch.zeros_like(a[:1])])           # tracks * frames - 1 slots -> tracks * frames
+        return full.view(tracks, frames, *a.shape[1:])[:, f - 1].contiguous()
+    pmap.reset()
+    images = torch.empty((tracks, H, W, 3), dtype=torch.uint8, device=dev)
+    last = {k: per_frame(out[k], 0) for k in ("xy", "desc", "nodes", "n")}
+    for f in range(1, frames):
+        cur = {k: per_frame(out[k], f) for k in ("xy", "desc", "nodes", "n")}
+        pair = {k: per_pair(out[k], f) for k in ("matches", "best", "F")}
+        pmap.step(last, cur, pair, bgr[:, f].contiguous(), K)
+        pmap.render(view, W, H, out=(images, None))              # stream-ordered behind the step: no wait in between
+        ctx.synchronize()
+        host = images.cpu().numpy()
+        for t in range(tracks):
+            write_ppm(os.path.join(out_dir, f"track{t}_step{f:02d}.ppm"), host[t])
+        last = cur
+    sizes = pmap.view()["sizes"]
+    print(f"{tracks * (frames - 1)} images of {W} x {H} in {out_dir}/; map points per track: {[int(s) for s in sizes]}")
+    pmap.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -430,6 +430,96 @@ int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, 
                           const float *h_K, float radius, uint32_t dist_threshold, float reproj_threshold_sq, float *d_xy,
                           uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches, int32_t *d_best, float *d_F);
 
+/* ------------------------------------------------------------ the view of the map (Display, headless)
+ * What the reference shows in its Pangolin window (include/Display.h, src/display.cpp; fed from src/vslam.cpp:264-276), as
+ * images in device memory: one image per track, from any viewpoint, the map points as squares of their stored colour and one
+ * wire frustum per recorded frame (draw_box, src/display.cpp:118-152).  THIS TEXT and tests/ref_render.py are the contract;
+ * OpenGL is not (no claim is made that Pangolin lights the same pixels).
+ *
+ * Eye space: x right, y down, z forward -- the convention of the project's cameras (c1 = [K | 0]).
+ * Arithmetic: every f32 input (coordinates, poses, the view) is widened to f64; products and sums run left to right in f64,
+ * never fused; division, floor and ceil are IEEE; one rounding to f32 where a depth becomes a key.  xf(M, p) below is
+ *     r_i = ((M[i][0] * p.x + M[i][1] * p.y) + M[i][2] * p.z) + M[i][3]        i = 0, 1, 2   (rows 0..2 of a row-major 4 x 4)
+ * and mix(a, b, t) = a * (1 - t) + b * t  (so that t = 0 gives a and t = 1 gives b exactly).
+ *
+ * Primitives of a track, in order; the ORDER INDEX breaks depth ties (the lower index wins):
+ *   1. its map points 0 .. n - 1, n = d_sizes[track] clamped to 0 .. map_stride  (AS_REFERENCE: n = ceil(size / 4), below);
+ *   2. with VSLAM_RENDER_FRUSTA, for frames 0 .. frames - 1 the eight segments of draw_box in the order of
+ *      src/display.cpp:129-148: order index n + 8 * frame + s.  With O = (0, 0, 0), w = box_w, h = w * box_h_ratio,
+ *      z = w * box_z_ratio (both products in f32, as draw_box forms them):
+ *        s = 0..3  O -> (w, h, z), O -> (w, -h, z), O -> (-w, -h, z), O -> (-w, h, z)
+ *        s = 4..7  (w, h, z) -> (w, -h, z), (-w, h, z) -> (-w, -h, z), (-w, h, z) -> (w, h, z), (-w, -h, z) -> (w, -h, z)
+ * A map point: e = xf(mv, (x, y, z)) -- the stored w is ignored, as glVertex3d ignores it.  Drawn iff the three of e are
+ *   finite and z_near <= e.z <= z_far.  px = floor(fu * e.x / e.z + u0), py = floor(fv * e.y / e.z + v0) (the product first,
+ *   then the quotient, then the sum); a point with |px| or |py| above 2^30 is not drawn.  It covers the pixels
+ *   px - (s - 1) / 2 .. px + s / 2 by py - (s - 1) / 2 .. py + s / 2 (s = point_size, integer division), clipped to the image,
+ *   each with depth (float) e.z.
+ * A frustum segment A -> B (camera coordinates): a = xf(mv, xf(pose, A)), b likewise, nothing rounded in between
+ *   (glMultTransposeMatrixf(pose) of a row-major pose is pose * p).  Dropped if a coordinate is not finite.
+ *   (i)   z clip: dropped if both a.z, b.z < z_near or both > z_far.  An endpoint p with p.z < z_near is replaced by
+ *         (mix(a.x, b.x, t), mix(a.y, b.y, t), z_near) with t = (z_near - a.z) / (b.z - a.z); with p.z > z_far likewise with
+ *         z_far.  Both replacements are computed from the ORIGINAL a and b.
+ *   (ii)  projection of both ends: U = fu * x / z + u0, V = fv * y / z + v0, iz = 1 / z; dropped if one is not finite.
+ *   (iii) Liang-Barsky against the rectangle [-0.5, width + 0.5] x [-0.5, height + 0.5] (half pixels: a run cut at two
+ *         opposite borders then steps from pixel centre to pixel centre, where floor is safe from the last bit of a sum),
+ *         s0 = 0, s1 = 1, dU = Ub - Ua, dV = Vb - Va,
+ *         for (p, q) in (-dU, Ua + 0.5), (dU, (width + 0.5) - Ua), (-dV, Va + 0.5), (dV, (height + 0.5) - Va):
+ *             p == 0: dropped if q < 0;   p < 0: r = q / p, dropped if r > s1, s0 = max(s0, r);
+ *             p > 0: r = q / p, dropped if r < s0, s1 = min(s1, r);
+ *         the ends become mix(., ., s0) and mix(., ., s1) of U, V and iz (from the unclipped ends).  An end inside the image is
+ *         therefore never moved, and the work per segment is O(width + height) whatever the pose.
+ *   (iv)  m = max(|Ub - Ua|, |Vb - Va|) of the clipped ends; dropped unless m <= 65536; n = max(1, ceil(m)); the samples
+ *         k = 0 .. n at t = k / n: pixel (floor(mix(Ua, Ub, t)), floor(mix(Va, Vb, t))), kept if inside the image, with depth
+ *         (float)(1 / mix(iza, izb, t)): 1 / z is linear on the screen, so the depth is perspective-correct.
+ * Winner per pixel: the smallest 64-bit key (bits of the f32 depth) << 32 | order index (positive floats order as their bit
+ * patterns; an integer minimum does not depend on arrival order, so the image is bitwise reproducible).  The pixel gets the
+ * winner's colour -- a point's stored (b, g, r) as is, frustum_bgr for a segment -- or background_bgr without a winner.
+ * VSLAM_RENDER_AS_REFERENCE reproduces what draw_points_colors actually submits (src/display.cpp:97-116): its loop runs
+ *   `i < size; i += 4` over a FLAT float index, so only points 0 .. ceil(size / 4) - 1 are drawn, and the colour goes through
+ *   glColor3b(colors.x, colors.y, colors.z): the stored B, G, R taken as SIGNED bytes and as red, green, blue.
+ *   [OpenGL, from memory] unpinned: a signed byte c maps to (2c + 1) / 255, negative values clamp to 0, so a stored channel c
+ *   becomes 2c + 1 for c < 128 and 0 otherwise; output R comes from stored B, output G from stored G, output B from stored R.
+ *
+ * d_points [tracks][map_stride][4] f32, d_colors [tracks][map_stride][3] u8, d_sizes [tracks] int32; d_pose
+ * [tracks][pose_stride][16] f32 (row-major 4 x 4; may be NULL when frames == 0 or VSLAM_RENDER_FRUSTA is not set),
+ * 0 <= frames <= pose_stride; d_points is 16-byte and d_depth_out 4-byte aligned (VSLAM_ERR_INVALID otherwise).  d_bgr_out [tracks][height][row_stride] u8, row_stride >= 3 * width; bytes past 3 * width in a
+ * row are not written.  d_depth_out (may be NULL) [tracks][height][width] f32: the winner's depth, +inf where nothing was drawn.
+ * Both calls are stream-ordered on the context, take their key plane ([tracks][height][width] u64) from the context's grow-only
+ * arena, do not synchronise (except when that plane has to grow: the arena then waits for the stream before it frees the old
+ * block, as for every workspace) and do not write to the map.  VSLAM_ERR_INVALID, before anything is queued, for: a null pointer,
+ * a non-positive size (tracks, map_stride, width, height; frames < 0; pose_stride < frames), row_stride < 3 * width,
+ * point_size outside 1..15, z_near <= 0 (or not finite), z_far < z_near, a track range outside the map.  VSLAM_ERR_CAPACITY for
+ * width or height above 16384, more than 65535 tracks or more than 2^20 frames.                                                                                      */
+#define VSLAM_RENDER_FRUSTA 1
+#define VSLAM_RENDER_AS_REFERENCE 2
+typedef struct vslam_view {
+    float mv[16];              /* world -> eye, row-major 4 x 4, rows 0..2 used (affine)            */
+    float fu, fv, u0, v0;      /* pinhole of the viewer                                              */
+    float z_near, z_far;       /* a primitive sample is drawn iff z_near <= eye z <= z_far           */
+    int32_t point_size;        /* side of the square a map point covers, 1..15                       */
+    int32_t flags;             /* VSLAM_RENDER_FRUSTA | VSLAM_RENDER_AS_REFERENCE                     */
+    float box_w, box_h_ratio, box_z_ratio;   /* draw_box: 1.0, 0.75, 0.6 (include/Display.h:34)      */
+    uint8_t background_bgr[3], frustum_bgr[3];   /* (0,0,0) and blue = (255,0,0), src/display.cpp:52 */
+} vslam_view;
+/* Host only, no context.  The numbers of src/display.cpp:25-26: look_at from eye (-2, 2, -2) to (0, 0, 0) with up (0, 1, 0),
+ * focal 420 / 420, centre (width / 2, height / 2) in integer division, near 0.2, far 10000; point size 1, VSLAM_RENDER_FRUSTA,
+ * the draw_box defaults, black background, blue frusta.                                                                    */
+int vslam_view_default(int width, int height, vslam_view *out);
+/* In double on the host: f = normalize(target - eye), r = normalize(cross(f, up)), d = cross(f, r); the rows of the rotation
+ * R are r, d, f, the translation is -(R * eye); rounded once to f32; row 3 = (0, 0, 0, 1).  normalize(v) = v / sqrt((v.x * v.x
+ * + v.y * v.y) + v.z * v.z), cross(a, b) = (a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x), a row of
+ * R * eye = (R0 * eye.x + R1 * eye.y) + R2 * eye.z.  VSLAM_ERR_DEGENERATE when eye == target or up is parallel to the
+ * viewing direction (mv_out is then untouched).                                                                            */
+int vslam_view_look_at(const double eye[3], const double target[3], const double up[3], float mv_out[16]);
+int vslam_render_points(vslam_ctx *ctx, const float *d_points, const uint8_t *d_colors, const int32_t *d_sizes,
+                        int tracks, int map_stride, const float *d_pose, int frames, int pose_stride,
+                        const vslam_view *h_view, int width, int height, int row_stride,
+                        uint8_t *d_bgr_out, float *d_depth_out /* may be NULL */);
+/* vslam_render_points over the map's own arrays (vslam_map_view) for tracks track_lo .. track_lo + track_count - 1 and the
+ * frames recorded so far; the output arrays have track_count slots.                                                       */
+int vslam_map_render(vslam_ctx *ctx, vslam_map *map, int track_lo, int track_count, const vslam_view *h_view,
+                     int width, int height, int row_stride, uint8_t *d_bgr_out, float *d_depth_out);
+
 /* ------------------------------------------------------------------ pipeline */
 /* match_features(frame1, frame2, rf, matches, F), src/Frame.cpp:82-105, for a batch of pairs
  * whose features are already on the device: match -> sets -> RANSAC -> inlier matches.

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvslam_amd.so")
 SOURCES = ["capi.hip", "match.hip", "ransac_sets.hip", "ransac_solve.hip", "ransac_count.hip", "ransac_select.hip",
            "kdtree.hip", "gray.hip", "response.hip", "select.hip", "blur.hip",
-           "brief.hip", "orb_grid.hip", "pose.hip", "assoc.hip", "map.hip", "multi.hip", "pipeline.hip"]
+           "brief.hip", "orb_grid.hip", "pose.hip", "assoc.hip", "map.hip", "render.hip", "multi.hip", "pipeline.hip"]
 HEADERS = ["ctx.h", "introselect.h", "image_common.h", "ransac_svd.h", "ransac_residual.h",
            os.path.join("..", "..", "include", "vslam_amd.h"),
            os.path.join("..", "..", "include", "vslam_brief_pattern_31.h")]
@@ -73,7 +73,7 @@ def _build(hipcc, OBJDIR, LIB, extra, force, verbose):
 
 
 HOST_LIB = os.path.join(HERE, "libvslam_host.so")
-HOST_SRCS = [os.path.join(HERE, "host", f) for f in ("adapters.cpp", "kdtree_nodes.cpp", "ingest.cpp", "pointmap.cpp")]
+HOST_SRCS = [os.path.join(HERE, "host", f) for f in ("adapters.cpp", "kdtree_nodes.cpp", "ingest.cpp", "pointmap.cpp", "display.cpp")]
 HOST_HDRS = [os.path.join(HERE, "host", "host_internal.h")]
 INCLUDE = os.path.join(HERE, "..", "include")
 

@@ -30,6 +30,7 @@ SYMBOLS = [
     "vslam_match_features",
     "vslam_map_create", "vslam_map_destroy", "vslam_map_reset", "vslam_map_step", "vslam_map_view", "vslam_map_observations",
     "vslam_track_sequences",
+    "vslam_view_default", "vslam_view_look_at", "vslam_render_points", "vslam_map_render",
     "vslam_frontend_pairs", "vslam_frontend_sequence", "vslam_pack_records",
     "vslam_host_alloc", "vslam_host_free", "vslam_upload_async", "vslam_upload_fence", "vslam_upload_wait", "vslam_download_async",
     "vslam_shard_range", "vslam_multi_create", "vslam_multi_destroy", "vslam_multi_size", "vslam_multi_ctx", "vslam_multi_last_error",
@@ -59,6 +60,52 @@ class MapArrays(C.Structure):   # vslam_map_arrays
 
 class VslamError(RuntimeError):
     pass
+
+
+RENDER_FRUSTA = 1
+RENDER_AS_REFERENCE = 2
+
+
+class View(C.Structure):   # vslam_view
+    """The viewer of vslam_render_points / vslam_map_render.  View.default(w, h) is the reference's window
+    (src/display.cpp:25-26); View.look_at(eye, target, up, ...) places the viewer (vslam_view_look_at).  The fields are the
+    struct's and can be set freely (point_size, flags, z_near, ...)."""
+    _fields_ = [("mv", C.c_float * 16), ("fu", C.c_float), ("fv", C.c_float), ("u0", C.c_float), ("v0", C.c_float),
+                ("z_near", C.c_float), ("z_far", C.c_float), ("point_size", C.c_int32), ("flags", C.c_int32),
+                ("box_w", C.c_float), ("box_h_ratio", C.c_float), ("box_z_ratio", C.c_float),
+                ("background_bgr", C.c_uint8 * 3), ("frustum_bgr", C.c_uint8 * 3)]
+
+    @classmethod
+    def default(cls, width, height, lib=None):
+        lib = lib or load_library()
+        v = cls()
+        rc = lib.vslam_view_default(C.c_int(width), C.c_int(height), C.byref(v))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_view_default({width}, {height})")
+        return v
+
+    @classmethod
+    def look_at(cls, eye, target, up, width, height, lib=None, **fields):
+        """View.default(width, height) seen from `eye` towards `target`; `fields` overwrite struct members."""
+        lib = lib or load_library()
+        v = cls.default(width, height, lib)
+        d3 = C.c_double * 3
+        rc = lib.vslam_view_look_at(d3(*[float(x) for x in eye]), d3(*[float(x) for x in target]), d3(*[float(x) for x in up]), v.mv)
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_view_look_at({eye}, {target}, {up})")
+        for k, val in fields.items():
+            if k in ("background_bgr", "frustum_bgr"):
+                val = (C.c_uint8 * 3)(*val)
+            setattr(v, k, val)
+        return v
+
+    def copy(self, **fields):
+        v = type(self).from_buffer_copy(self)
+        for k, val in fields.items():
+            if k in ("background_bgr", "frustum_bgr"):
+                val = (C.c_uint8 * 3)(*val)
+            setattr(v, k, val)
+        return v
 
 
 def load_library(path=LIB_PATH):
@@ -602,6 +649,33 @@ class Context:
             _ptr(out["best"]), _ptr(out["F"])))
         return out
 
+    def render_points(self, points, colors, sizes, view, width, height, pose=None, frames=None, depth=False, row_stride=None,
+                      out=None):
+        """vslam_render_points: points (T, M, 4) f32, colors (T, M, 3) u8, sizes (T,) i32, pose (T, P, 16) f32 or None ->
+        bgr (T, H, W, 3) u8 -- (T, H, row_stride) when row_stride is given -- and, with depth=True, (T, H, W) f32 as well.
+        `out` = (bgr, depth or None) tensors to write into instead of new ones."""
+        torch = self.torch
+        T, M, _ = points.shape
+        self._dev(points, torch.float32, "points"); self._dev(colors, torch.uint8, "colors"); self._dev(sizes, torch.int32, "sizes")
+        self._dev(pose, torch.float32, "pose")
+        P = pose.shape[1] if pose is not None else 0
+        frames = P if frames is None else frames
+        bgr, dep = self._render_outputs(T, width, height, depth, row_stride, out)
+        self._check(self.lib.vslam_render_points(
+            self.handle, _ptr(points), _ptr(colors), _ptr(sizes), C.c_int(T), C.c_int(M), _ptr(pose), C.c_int(frames), C.c_int(P),
+            C.byref(view), C.c_int(width), C.c_int(height), C.c_int(row_stride or 3 * width), _ptr(bgr), _ptr(dep)))
+        return (bgr, dep) if depth else bgr
+
+    def _render_outputs(self, T, width, height, depth, row_stride, out):
+        torch = self.torch
+        if out is not None:
+            return out
+        shape = (T, height, width, 3) if row_stride is None else (T, height, row_stride)
+        bgr = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        dep = torch.empty((T, height, width), dtype=torch.float32, device=self.device) if depth else None
+        self._ready()
+        return bgr, dep
+
 
 class PointMap:
     """A vslam_map: the reference's PointMap and per-frame map_point_ids / R_t / pose for `tracks` sequences, resident on the
@@ -661,6 +735,16 @@ class PointMap:
                     sizes=get(a.d_sizes, (T,), np.int32), map_point_ids=get(a.d_map_point_ids, (T, Fr, Kp), np.int32),
                     R_t=get(a.d_R_t, (T, Fr, 16), np.float32), pose=get(a.d_pose, (T, Fr, 16), np.float32),
                     obs_counts=get(a.d_obs_counts, (T, M), np.int32), n_obs=get(a.d_n_obs, (T,), np.int32))
+
+    def render(self, view, width, height, tracks=None, depth=False, row_stride=None, out=None):
+        """vslam_map_render: the map as images on the device, one per track -- all of them, or tracks = (lo, count).  Returns
+        bgr (count, H, W, 3) u8 ((count, H, row_stride) when row_stride is given) and, with depth=True, (count, H, W) f32."""
+        lo, count = (0, self.tracks) if tracks is None else tracks
+        bgr, dep = self.ctx._render_outputs(max(count, 0), width, height, depth, row_stride, out)
+        self.ctx._check(self.lib.vslam_map_render(self.ctx.handle, self.handle, C.c_int(lo), C.c_int(count), C.byref(view),
+                                                  C.c_int(width), C.c_int(height), C.c_int(row_stride or 3 * width), _ptr(bgr),
+                                                  _ptr(dep)))
+        return (bgr, dep) if depth else bgr
 
     def observations(self):
         """(offsets [tracks][map_capacity + 1], frame_ids, point_ids [tracks][obs_capacity]) as cuda tensors, stream-ordered;

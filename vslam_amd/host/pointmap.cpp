@@ -129,6 +129,13 @@ void map_step(PointMap &pm, const std::vector<std::pair<int, int>> &matches, con
     d.recorded = fid;
     check(vslam_ctx_synchronize(context()), "PointMap: map_step (a capacity of the map, or more than 16 acceptable hits)");
 }
+
+namespace detail {
+vslam_map *device_map(PointMap &pm) {
+    if (!pm.device) throw std::logic_error("PointMap: vslam::map_create first");
+    return pm.device->map;
+}
+}  // namespace detail
 }  // namespace vslam
 
 void PointMap::sync_to_host() {
