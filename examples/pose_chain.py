@@ -4,7 +4,11 @@ pairs as tickets of a pipeline, each ticket = extract x2 + match + RANSAC + extr
 (vslam_pipeline_submit_pairs_pose); then the map-association block on a batch's own triangulated points
 (vslam_associate_map_points).  Only poses, counts and the few numbers printed here leave the device.
 
-    python examples/pose_chain.py
+    python examples/pose_chain.py [--refit]
+
+--refit: VSLAM_OPT_POSE_REFIT on every context of the pipeline -- each ticket's RANSAC winner is refitted over all its inliers
+(vslam_refit_fundamental) before the pose stages, which then work from the refitted F -- and, for the first batch, the stage by
+itself as a ticket of its own: the mean Sampson distance of every pair's inliers before and after (d_stats).
 """
 import os
 import sys
@@ -20,6 +24,9 @@ def main():
     pairs, width, height, max_corners, hyp = 4, 640, 480, 1000, 512
     dev = torch.device("cuda", 0)
     pipe = capi.Pipeline(0, 2)                                   # two batches in flight
+    refit = "--refit" in sys.argv[1:]
+    if refit:
+        pipe.set_option(capi.Context.OPT_POSE_REFIT, 1)
     cos_a, sin_a = synth.keypoint_rotation()
     K = np.array([[525.0, 0, width // 2], [0, 525.0, height // 2], [0, 0, 1]], np.float32)   # src/vslam.cpp:32
     batches = [torch.from_numpy(synth.frames_numpy(20 + i, pairs, width, height)).to(dev) for i in range(3)]
@@ -32,6 +39,16 @@ def main():
         tickets.append(pipe.submit_pairs_pose(batches[i], pairs, max_corners, cos_a, sin_a, None, seeds[i], hyp, 10.0, K, outs[i % 2]))
     for i in (1, 2):
         report(pipe, tickets[i], outs[i % 2], i, pairs)
+
+    if refit:   # the stage by itself: front end, then the refit with its statistics, one ticket
+        t, ctx = pipe.acquire()
+        fe = ctx.frontend_pairs(batches[0], pairs, max_corners, cos_a, sin_a, None, seeds[0], hyp, 10.0)
+        _, stats = ctx.refit_fundamental(fe["xy"][:pairs].contiguous(), fe["xy"][pairs:].contiguous(), fe["matches"], fe["best"], fe["F"])
+        pipe.commit(t)
+        pipe.wait(t)
+        for p, (n, before, after, ratio) in enumerate(stats.cpu().numpy()):
+            print(f"refit, batch 0 pair {p}: {int(n)} inliers, mean Sampson distance {before:.4f} -> {after:.4f} px^2, "
+                  f"lambda9 / lambda8 = {ratio:.2e}")
 
     # the association block on the last batch: its triangulated points as the map (one observation each: the matched keypoint of
     # the first frame), looked up in the second frame's k-d tree, radius 2, Hamming threshold 64 (src/vslam.cpp:129-161)

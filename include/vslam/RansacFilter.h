@@ -37,6 +37,14 @@ class RansacFilter {
                                                        const std::vector<std::pair<int, int>> &matches,
                                                        const cv::Mat &F, std::vector<bool> &inliers);
 
+    // addition (the reference returns the winner as fitted to its 8 sampled, un-normalised points; `//TODO: normalize` at
+    // src/RansacFilter.cpp:40): `fundamental` (3 x 3 CV_32F, as find_fundamental left it) refitted IN PLACE over the matches
+    // flagged in `inliers` -- Hartley-normalised, rank 2, unit Frobenius norm, the sign of the F passed in
+    // (vslam_refit_fundamental, include/vslam_amd.h).  Left as it is with fewer than 8 flagged matches or points on one spot.
+    void refit_fundamental(const std::vector<cv::Point2f> &p1, const std::vector<cv::Point2f> &p2,
+                           const std::vector<std::pair<int, int>> &matches, const std::vector<bool> &inliers,
+                           cv::Mat &fundamental) const;
+
     // addition (the reference has no seed parameter): fix the mt19937 seed of the next draws
     void set_seed(u32 seed) { seed_ = seed; has_seed_ = true; }
     const std::vector<std::vector<int>> &sets() const { return ransac_sets; }

@@ -5,6 +5,7 @@
 #include <iostream>
 #include <vector>
 
+#include "../vslam_amd.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -45,6 +46,13 @@ void extract_Rt(const cv::Mat &fundamental, const cv::Mat &K, cv::Mat &rotation,
 void triangulate(const cv::Mat &p1, const cv::Mat &p2, const cv::Mat &c1, const cv::Mat &c2, cv::Mat &points_4d);
 
 namespace vslam {
+// For callers whose features and RANSAC results are already on the device (vslam_match_features / vslam_frontend_*): the
+// winners d_F [batch][9] refitted in place over their inlier matches, stream-ordered on `ctx` -- vslam_refit_fundamental with
+// d_F_out = d_F_in; throws std::runtime_error with vslam_last_error on failure.  d_stats [batch][4] f64 or nullptr.
+// RansacFilter::refit_fundamental is the host-vector form.
+void refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
+                       int kp_stride, float *d_F, f64 *d_stats = nullptr);
+
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)
 // (pm.points.rowRange(0, pm.size)); c2: 3 x 4.  Map point i is projected, dropped unless it lands inside [0, W) x [0, H),

@@ -129,6 +129,11 @@ const int8_t *vslam_brief_pattern_31(void);
  *       4 behind the screen, 5 not forked at all (in line on the main stream, at the end of extraction).  The call's last
  *       kernel waits for it.  Same results; a tuning knob.                                                             */
 #define VSLAM_OPT_TREE_FORK 9
+/*   VSLAM_OPT_POSE_REFIT  0 (default): nothing changes.  1: vslam_frontend_pairs_pose (and so vslam_pipeline_submit_pairs_pose)
+ *       and vslam_track_sequences run vslam_refit_fundamental on d_F, in place, between RANSAC and extract_Rt / the map steps:
+ *       the pose, triangulation, filter and map stages get the refitted F, d_F holds it (so do records packed from it);
+ *       d_best, d_matches and the inlier set are what they are without the option.                                       */
+#define VSLAM_OPT_POSE_REFIT 10
 int vslam_ctx_set_option(vslam_ctx *ctx, int option, int value);
 
 /* device memory + copies for hosts that have no other allocator (the C++ adapters) */
@@ -215,6 +220,40 @@ int vslam_ransac_evaluate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2
                           const int32_t *d_pairs, const int32_t *d_m, const float *d_hypF, int batch,
                           int kp_stride, int hyp, float threshold, float *d_F, uint8_t *d_mask,
                           int32_t *d_best, int32_t *d_matches, int32_t *d_hyp_count, float *d_hyp_sum);
+
+/* The step find_fundamental leaves undone (src/RansacFilter.cpp:36-67 returns the winner as fitted to its 8 sampled,
+ * un-normalised points; `//TODO: normalize` at :40): the winning F refitted over ALL its inliers.  THIS TEXT and
+ * tests/ref_refit.py are the contract.
+ * Inputs per item b: the compacted inlier matches d_matches[b][0 .. n), n = d_best[b][3] (clamped to 0 .. kp_stride), as
+ * vslam_ransac_evaluate / vslam_match_features write them, into d_xy1 / d_xy2 [batch][kp_stride][2]; d_F_in [batch][9].  A match
+ * with an index outside 0 .. kp_stride - 1 is skipped and not counted.  Every f32 input is widened to f64 and ALL arithmetic
+ * is f64, never fused:
+ *   1. Hartley normalisation per image: c = centroid, d = mean Euclidean distance to c, s = sqrt(2) / d,
+ *      T = [[s, 0, -s c.x], [0, s, -s c.y], [0, 0, 1]];
+ *   2. M = A^t A (9 x 9) over the normalised correspondences, the rows of A as in src/RansacFilter.cpp:81-89:
+ *      u2 u1, u2 v1, u2, v2 u1, v2 v1, v2, u1, v1, 1;
+ *   3. f = the eigenvector of M's smallest eigenvalue by cyclic Jacobi (rows (0,1), (0,2) .. (7,8)), until
+ *      sqrt(sum of the squared off-diagonal entries) <= 2^-52 * trace or 30 sweeps; Fh = f as a row-major 3 x 3;
+ *   4. rank 2: the SVD of Fh (one-sided Jacobi), the smallest singular value set to 0, recomposed;
+ *   5. F = T2^t Fh T1, divided by its Frobenius norm;
+ *   6. negated if sum F_ij * F_in_ij < 0 (F_in is the RANSAC winner: the refit continues it);
+ *   7. rounded once to f32 into d_F_out [batch][9] (may be d_F_in itself).
+ * An item is LEFT ALONE -- d_F_out[b] = d_F_in[b] bit for bit, written by the same kernel -- when there is no winner
+ * (d_best[b][0] < 0), when fewer than 8 correspondences are counted, when d == 0 in either image, or when an entry of the
+ * result is not finite.  None of this raises the error word.
+ * d_stats (may be NULL) [batch][4] f64: [0] correspondences used; [1] the mean TRUE Sampson distance
+ * e^2 / (Fx1_0^2 + Fx1_1^2 + Ftx2_0^2 + Ftx2_1^2), e = x2^t F x1, of those correspondences under F_in (not the expression of
+ * src/RansacFilter.cpp:126); [2] the same under F_out as written (the f32 values); [3] lambda_9 / lambda_8 of M, smallest over
+ * second smallest eigenvalue (near 1: the null vector is not isolated).  For an item left alone [0] is the count that was
+ * found and [1..3] are NaN.
+ * Deterministic: no floating-point atomics; every sum is a strided partial sum per lane (256 lanes), a butterfly inside the
+ * wave, then the wave sums in wave order -- the order depends on n alone, so a pair gives the same bits in every run, in any
+ * batch, at any position.  One workgroup per item, any n up to kp_stride.
+ * Stream-ordered on the context; allocates nothing and does not synchronise.  VSLAM_ERR_INVALID, before anything is queued,
+ * for a null pointer (d_stats excepted), batch <= 0 or kp_stride <= 0.                                                   */
+int vslam_refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const int32_t *d_matches,
+                            const int32_t *d_best, int batch, int kp_stride, const float *d_F_in,
+                            float *d_F_out /* may alias d_F_in */, double *d_stats /* [batch][4], may be NULL */);
 
 /* ------------------------------------------------------------------ k-d tree */
 /* Replaces construct_kdtree(frame_kdtree&, points), src/KDTree.cpp:107-143.  The tree is the

@@ -24,7 +24,7 @@ SYMBOLS = [
     "vslam_last_error", "vslam_ctx_workspace_bytes", "vslam_version", "vslam_brief_pattern_31", "vslam_dev_alloc", "vslam_dev_free", "vslam_copy_h2d",
     "vslam_copy_d2h", "vslam_debug_stream_copy", "vslam_debug_valu_calib", "vslam_prof_enable", "vslam_prof_reset", "vslam_prof_count", "vslam_prof_get",
     "vslam_match_knn2_ratio", "vslam_ransac_sets", "vslam_ransac_fundamental", "vslam_ransac_solve",
-    "vslam_ransac_evaluate", "vslam_kdtree_build",
+    "vslam_ransac_evaluate", "vslam_refit_fundamental", "vslam_kdtree_build",
     "vslam_kdtree_radius", "vslam_kdtree_nearest", "vslam_kdtree_cell_table", "vslam_extract_features", "vslam_extract_features_grid", "vslam_triangulate_points", "vslam_frontend_pairs_pose", "vslam_pipeline_batches_redone", "vslam_corner_stats", "vslam_bgr2gray", "vslam_min_eigen",
     "vslam_good_features", "vslam_gaussian7", "vslam_orb_describe", "vslam_extract_Rt", "vslam_triangulate", "vslam_associate_map_points", "vslam_reprojection_filter",
     "vslam_match_features",
@@ -198,6 +198,7 @@ class Context:
     OPT_CORNER_LIST_CAP = 7
     OPT_MATCH_FORM = 8
     OPT_TREE_FORK = 9
+    OPT_POSE_REFIT = 10
 
     def set_option(self, option, value):
         self._check(self.lib.vslam_ctx_set_option(self.handle, C.c_int(option), C.c_int(int(value))))
@@ -311,6 +312,22 @@ class Context:
             C.c_float(threshold), _ptr(out["F"]), _ptr(out["mask"]), _ptr(out["best"]), _ptr(out["matches"]),
             _ptr(out["hyp_count"]), _ptr(out["hyp_sum"])))
         return out
+
+    def refit_fundamental(self, xy1, xy2, matches, best, F, out=None, want_stats=True):
+        """vslam_refit_fundamental: the RANSAC winner F (B, 9) refitted over its inlier matches (B, K, 2) / best (B, 4) as
+        ransac_* / match_features return them.  Returns (F_out (B, 9) f32, stats (B, 4) f64 or None); out=F refits in place."""
+        torch = self.torch
+        B, K, _ = xy1.shape
+        for t, dt, nm in ((xy1, torch.float32, "xy1"), (xy2, torch.float32, "xy2"), (matches, torch.int32, "matches"),
+                          (best, torch.int32, "best"), (F, torch.float32, "F"), (out, torch.float32, "out")):
+            self._dev(t, dt, nm)
+        if out is None:
+            out = torch.empty((B, 9), dtype=torch.float32, device=xy1.device)
+        stats = torch.empty((B, 4), dtype=torch.float64, device=xy1.device) if want_stats else None
+        self._ready()
+        self._check(self.lib.vslam_refit_fundamental(self.handle, _ptr(xy1), _ptr(xy2), _ptr(matches), _ptr(best), C.c_int(B),
+                                                     C.c_int(K), _ptr(F), _ptr(out), _ptr(stats)))
+        return out, stats
 
     def kdtree_build(self, xy, n):
         torch = self.torch

@@ -415,6 +415,11 @@ int vslam_ctx_set_option(vslam_ctx *ctx, int option, int value) {
         ctx->corner_window_pct = value;
         return VSLAM_OK;
     }
+    if (option == VSLAM_OPT_POSE_REFIT) {
+        VS_REQUIRE(ctx, value == 0 || value == 1, VSLAM_ERR_INVALID);
+        ctx->pose_refit = value != 0;
+        return VSLAM_OK;
+    }
     if (option == VSLAM_OPT_TREE_FORK) {
         VS_REQUIRE(ctx, value >= -1 && value <= 5, VSLAM_ERR_INVALID);
         ctx->tree_fork = value;
@@ -926,6 +931,8 @@ int vslam_frontend_pairs_pose(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, i
         VS_HIP(ctx, hipMemsetAsync(ids, 0xFF, sizeof(int32_t) * half, ctx->stream));
         d_map_point_ids = ids;
     }
+    if (ctx->pose_refit)   // VSLAM_OPT_POSE_REFIT: every later stage, and the caller, gets the winner refitted over its inliers
+        if ((rc = vs_launch_refit(ctx, xy1, xy2, d_matches, d_best, pairs, kp_stride, d_F, d_F, nullptr))) return rc;
     if ((rc = vs_launch_extract_Rt(ctx, d_F, d_best, pairs, h_K, pose->d_R, pose->d_t, pose->d_c2))) return rc;
     if ((rc = vs_launch_triangulate(ctx, xy1, xy2, d_matches, d_best, pairs, kp_stride, h_K, pose->d_c2, pose->d_points4d))) return rc;
     return vs_launch_reproj_filter(ctx, pose->d_points4d, xy1, xy2, d_matches, d_best, pairs, kp_stride, h_K, pose->d_c2,

@@ -57,6 +57,7 @@ struct vslam_ctx {
     int match_form = 0;                         // VSLAM_OPT_MATCH_FORM: 0 default (FP4), 1 FP4, 2 int8
     int corner_window_pct = 135;                // VSLAM_OPT_CORNER_WINDOW_PCT
     int corner_list_cap = 0;                    // VSLAM_OPT_CORNER_LIST_CAP: 0 = 16 x max_corners + 4096, -1 = whole image
+    bool pose_refit = false;        // VSLAM_OPT_POSE_REFIT: the pose chain and the tracking loop refit F over its inliers (refit.hip)
     bool ransac_all_sums = false;   // VSLAM_OPT_RANSAC_ALL_SUMS: exact residual sum of every hypothesis (ransac_score_kernel)
     // where the corner detector's last batch left its per-frame counters (vslam_corner_stats reads them after a stream wait)
     const uint32_t *stat_counts = nullptr;
@@ -204,6 +205,9 @@ int vs_launch_ransac_evaluate(vslam_ctx *ctx, const float *xy1, const float *xy2
                               const int32_t *m, const float *hypF, int batch, int kp_stride, int hyp,
                               float threshold, float *F, uint8_t *mask, int32_t *best, int32_t *matches,
                               int32_t *hyp_count, float *hyp_sum);
+// the winner refitted over its inliers (refit.hip); F_out may be F_in
+int vs_launch_refit(vslam_ctx *ctx, const float *xy1, const float *xy2, const int32_t *matches, const int32_t *best, int batch,
+                    int kp_stride, const float *F_in, float *F_out, double *stats);
 int vs_launch_kdtree_build(vslam_ctx *ctx, const float *xy, const int32_t *n, int batch, int kp_stride,
                            int32_t *nodes);
 int vs_launch_kdtree_radius(vslam_ctx *ctx, const int32_t *nodes, const float *xy, const int32_t *n,

@@ -660,6 +660,8 @@ int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, 
     if ((rc = vslam_frontend_sequence(ctx, d_bgr, T * frames, width, height, row_stride, params, K, flat_seeds, hyp, threshold,
                                       d_xy, d_desc, d_nodes, d_n, d_matches, d_best, d_F)))
         return rc;
+    if (ctx->pose_refit)   // VSLAM_OPT_POSE_REFIT: all pairs at once (pair i = frames i, i + 1 of the flattened row), in place
+        if ((rc = vs_launch_refit(ctx, d_xy, d_xy + 2 * (size_t)K, d_matches, d_best, T * frames - 1, K, d_F, d_F, nullptr))) return rc;
     // Frame f of every track as one [tracks][...] batch: the pose and association launchers take items at a stride of one
     // frame, the flattened arrays hold a track's frames side by side.
     const size_t fK = (size_t)frames * K;

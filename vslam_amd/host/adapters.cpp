@@ -796,6 +796,54 @@ std::pair<int, float> RansacFilter::compute_fundamental_residual(const std::vect
     return {*c.hout<int32_t>(o_cnt), *c.hout<float>(o_sum)};
 }
 
+// the winner refitted over the flagged matches (vslam_refit_fundamental); an addition, like set_seed
+void RansacFilter::refit_fundamental(const std::vector<cv::Point2f> &p1, const std::vector<cv::Point2f> &p2,
+                                     const std::vector<std::pair<int, int>> &matches, const std::vector<bool> &inliers,
+                                     cv::Mat &fundamental) const {
+    if (inliers.size() != matches.size()) throw std::invalid_argument("refit_fundamental: one inlier flag per match");
+    if (fundamental.rows != 3 || fundamental.cols != 3 || fundamental.type() != CV_32FC1)
+        throw std::invalid_argument("refit_fundamental: fundamental must be a 3 x 3 CV_32F matrix");
+    Lock lk(g_mu);
+    const size_t M = matches.size();
+    const int stride = (int)std::max(std::max(p1.size(), p2.size()), std::max(M, (size_t)1));
+    Layout in, res, work;
+    const size_t o_best = in.add(16), o_F = in.add(36), o_xy1 = in.add(8 * (size_t)stride), o_xy2 = in.add(8 * (size_t)stride),
+                 o_match = in.add(8 * (size_t)stride);
+    const size_t o_out = res.add(36);
+    Call c(in, res, work);
+    for (int r = 0; r < 3; r++) std::memcpy(c.hin<float>(o_F) + 3 * r, fundamental.ptr<float>(r), sizeof(float) * 3);
+    if (!p1.empty()) std::memcpy(c.hin<float>(o_xy1), p1.data(), 8 * p1.size());
+    if (!p2.empty()) std::memcpy(c.hin<float>(o_xy2), p2.data(), 8 * p2.size());
+    int32_t *flat = c.hin<int32_t>(o_match);
+    int n = 0;
+    for (size_t i = 0; i < M; i++) {
+        if (!inliers[i]) continue;
+        flat[2 * n] = matches[i].first;
+        flat[2 * n + 1] = matches[i].second;
+        n++;
+    }
+    // indices past either point list are outside the slots that hold data: they must not reach zero-filled padding
+    for (int i = 0; i < n; i++)
+        if (flat[2 * i] < 0 || (size_t)flat[2 * i] >= p1.size() || flat[2 * i + 1] < 0 || (size_t)flat[2 * i + 1] >= p2.size())
+            throw std::out_of_range("refit_fundamental: a match index is outside its point list");
+    int32_t *best = c.hin<int32_t>(o_best);
+    best[0] = 0; best[1] = n; best[2] = 0; best[3] = n;
+    c.upload();
+    check(vslam_refit_fundamental(ctx(), c.din<float>(o_xy1), c.din<float>(o_xy2), c.din<int32_t>(o_match), c.din<int32_t>(o_best), 1,
+                                  stride, c.din<float>(o_F), c.dout<float>(o_out), nullptr),
+          "refit_fundamental");
+    c.download();
+    for (int r = 0; r < 3; r++) std::memcpy(fundamental.ptr<float>(r), c.hout<float>(o_out) + 3 * r, sizeof(float) * 3);
+}
+
+namespace vslam {
+void refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
+                       int kp_stride, float *d_F, f64 *d_stats) {
+    const int rc = vslam_refit_fundamental(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, d_F, d_F, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_refit_fundamental: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+}  // namespace vslam
+
 // -------------------------------------------------------------------------------------- Frame.h
 void initialize_frame(Frame &frame, const cv::Mat &image, long frame_id) {
     frame.image = image;   // shallow, aliases the capture buffer (src/Frame.cpp:4)
