@@ -4,11 +4,15 @@ pairs as tickets of a pipeline, each ticket = extract x2 + match + RANSAC + extr
 (vslam_pipeline_submit_pairs_pose); then the map-association block on a batch's own triangulated points
 (vslam_associate_map_points).  Only poses, counts and the few numbers printed here leave the device.
 
-    python examples/pose_chain.py [--refit]
+    python examples/pose_chain.py [--refit] [--refine]
 
 --refit: VSLAM_OPT_POSE_REFIT on every context of the pipeline -- each ticket's RANSAC winner is refitted over all its inliers
 (vslam_refit_fundamental) before the pose stages, which then work from the refitted F -- and, for the first batch, the stage by
 itself as a ticket of its own: the mean Sampson distance of every pair's inliers before and after (d_stats).
+
+--refine: VSLAM_OPT_POSE_REFINE on every context of the pipeline -- each ticket's pose and points go through the two-view bundle
+adjustment (vslam_refine_pairs) before the reprojection filter -- and, for the first batch, the chain by hand as a ticket of its
+own: per pair the mean squared reprojection error before and after (d_stats) and how many matches pass the filter.
 """
 import os
 import sys
@@ -27,6 +31,8 @@ def main():
     refit = "--refit" in sys.argv[1:]
     if refit:
         pipe.set_option(capi.Context.OPT_POSE_REFIT, 1)
+    if "--refine" in sys.argv[1:]:
+        pipe.set_option(capi.Context.OPT_POSE_REFINE, 1)
     cos_a, sin_a = synth.keypoint_rotation()
     K = np.array([[525.0, 0, width // 2], [0, 525.0, height // 2], [0, 0, 1]], np.float32)   # src/vslam.cpp:32
     batches = [torch.from_numpy(synth.frames_numpy(20 + i, pairs, width, height)).to(dev) for i in range(3)]
@@ -49,6 +55,22 @@ def main():
         for p, (n, before, after, ratio) in enumerate(stats.cpu().numpy()):
             print(f"refit, batch 0 pair {p}: {int(n)} inliers, mean Sampson distance {before:.4f} -> {after:.4f} px^2, "
                   f"lambda9 / lambda8 = {ratio:.2e}")
+
+    if "--refine" in sys.argv[1:]:   # the chain by hand: front end, pose, triangulation, then the adjustment with its statistics
+        t, ctx = pipe.acquire()
+        fe = ctx.frontend_pairs(batches[0], pairs, max_corners, cos_a, sin_a, None, seeds[0], hyp, 10.0)
+        xy1, xy2 = fe["xy"][:pairs].contiguous(), fe["xy"][pairs:].contiguous()
+        R, tr, c2 = ctx.extract_Rt(fe["F"], fe["best"], K)
+        pts = ctx.triangulate(xy1, xy2, fe["matches"], fe["best"], K, c2)
+        ids = torch.full((pairs, max_corners), -1, dtype=torch.int32, device=dev)
+        _, n_before, _ = ctx.reprojection_filter(pts, xy1, xy2, fe["matches"], fe["best"], K, c2, ids, 4.0)
+        _, _, c2, _, stats = ctx.refine_pairs(xy1, xy2, fe["matches"], fe["best"], K, R, tr, pts, 16.0, 20)
+        _, n_after, _ = ctx.reprojection_filter(pts, xy1, xy2, fe["matches"], fe["best"], K, c2, ids, 4.0)
+        pipe.commit(t)
+        pipe.wait(t)
+        for p, (n, before, after, steps) in enumerate(stats.cpu().numpy()):
+            print(f"refine, batch 0 pair {p}: {int(n)} matches, mean squared reprojection error {before:.4f} -> {after:.4f} px^2, "
+                  f"{int(n_before[p])} -> {int(n_after[p])} pass the filter")
 
     # the association block on the last batch: its triangulated points as the map (one observation each: the matched keypoint of
     # the first frame), looked up in the second frame's k-d tree, radius 2, Hamming threshold 64 (src/vslam.cpp:129-161)

@@ -53,6 +53,14 @@ namespace vslam {
 void refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
                        int kp_stride, float *d_F, f64 *d_stats = nullptr);
 
+// Two-view bundle adjustment of each pair's pose and points (vslam_refine_pairs, include/vslam_amd.h), in place on the device
+// arrays d_R [batch][9], d_t [batch][3], d_points4d [batch][kp_stride][4] as vslam_extract_Rt / vslam_triangulate wrote them;
+// d_c2 [batch][12] receives K [R | t].  K: 3 x 3 CV_32F.  Stream-ordered on `ctx`; throws std::runtime_error with
+// vslam_last_error on failure.  d_stats [batch][4] f64 or nullptr.
+void refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
+                  int kp_stride, const cv::Mat &K, float gate_sq, int max_iterations, float *d_R, float *d_t, float *d_c2,
+                  float *d_points4d, f64 *d_stats = nullptr);
+
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)
 // (pm.points.rowRange(0, pm.size)); c2: 3 x 4.  Map point i is projected, dropped unless it lands inside [0, W) x [0, H),

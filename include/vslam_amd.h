@@ -134,6 +134,13 @@ const int8_t *vslam_brief_pattern_31(void);
  *       the pose, triangulation, filter and map stages get the refitted F, d_F holds it (so do records packed from it);
  *       d_best, d_matches and the inlier set are what they are without the option.                                       */
 #define VSLAM_OPT_POSE_REFIT 10
+/*   VSLAM_OPT_POSE_REFINE  0 (default): nothing changes, no launch is added.  1: vslam_frontend_pairs_pose (and so
+ *       vslam_pipeline_submit_pairs_pose) runs vslam_refine_pairs in place on d_R / d_t / d_c2 / d_points4d between the
+ *       triangulation and the reprojection filter, with gate_sq = 4 x reproj_threshold_sq and 20 iterations: the filter and the
+ *       caller get the adjusted pose and points.  vslam_map_step / vslam_track_sequences triangulate directly after extract_Rt
+ *       and run the same adjustment there, so the pose entered into the map, the association, the filter and the appended points
+ *       all use the adjusted values.  Comes after VSLAM_OPT_POSE_REFIT when both are on.  Any other value: VSLAM_ERR_INVALID. */
+#define VSLAM_OPT_POSE_REFINE 11
 int vslam_ctx_set_option(vslam_ctx *ctx, int option, int value);
 
 /* device memory + copies for hosts that have no other allocator (the C++ adapters) */
@@ -254,6 +261,55 @@ int vslam_ransac_evaluate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2
 int vslam_refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const int32_t *d_matches,
                             const int32_t *d_best, int batch, int kp_stride, const float *d_F_in,
                             float *d_F_out /* may alias d_F_in */, double *d_stats /* [batch][4], may be NULL */);
+
+/* Two-view bundle adjustment of each pair's pose and points: the step the reference left as an empty `struct optimizer`
+ * (src/optimzer.cpp).  Within one pair there is one fixed camera [K | 0], one free camera K [R | t] and the pair's own points;
+ * the sum of the squared reprojection errors in both images is minimised over R, t (|t| = 1) and the points by
+ * Levenberg-Marquardt on the Schur-reduced 5 x 5 system.  THIS TEXT and tests/ref_refine.py are the contract.
+ * Inputs per item b: the compacted inlier matches d_matches[b][0 .. n), n = d_best[b][3] clamped to 0 .. kp_stride, into
+ * d_xy1 / d_xy2 [batch][kp_stride][2]; d_R [batch][9] (row-major), d_t [batch][3] as vslam_extract_Rt wrote them;
+ * d_points4d [batch][kp_stride][4] as vslam_triangulate wrote them (x, y, z, 1 in match slot i; the fourth entry is not read);
+ * h_K: 9 floats on the host, row-major.  Every f32 input is widened to f64 and ALL arithmetic is f64, never fused.  A match with
+ * an index outside 0 .. kp_stride - 1 is skipped.
+ * Projection of a point Y in camera coordinates: q_r = (K_r0 Y_0 + K_r1 Y_1) + K_r2 Y_2, (u, v) = (q_0 / q_2, q_1 / q_2).  In the
+ * first image Y = X; in the second Y = RX + t with (RX)_r = (R_r0 X_0 + R_r1 X_1) + R_r2 X_2.  The error of a match in an image
+ * is (u - x)^2 + (v - y)^2 against its keypoint (x, y).
+ *   1. PARTICIPATING matches, fixed once: X finite, X_2 > 0, (RX + t)_2 > 0 and the error <= gate_sq in each image separately,
+ *      all under the inputs as given.  The objective is the sum of both errors over the participating matches.
+ *   2. Start: R0 = R (3 I - R^t R) / 2 (one Newton step of the polar iteration: R comes from f32), t0 = t / |t|, the points as
+ *      given; lambda = 1e-3.
+ *   3. One iteration at (R, t, X), residual r = projection - keypoint.  Per point, with A(Y) = d(u, v)/dY =
+ *      [K_0. - u K_2. ; K_1. - v K_2.] / q_2:  J1x = A(X);  J2x = A(Y) R;  Jc = A(Y) [ -[RX]x | b1 | b2 ] (2 x 5), where e_k is the
+ *      axis of the smallest |t_k| (the lowest k on a tie), b1 = normalize(t x e_k), b2 = t x b1;
+ *      V = J1x^t J1x + J2x^t J2x, W = Jc^t J2x (5 x 3), g_x = J1x^t r_1 + J2x^t r_2, g_c = Jc^t r_2;
+ *      damping (Marquardt): V*_kk = V_kk + lambda max(V_kk, 2^-40), and the diagonal of Jc^t Jc times (1 + lambda) (no floor:
+ *      a reduced system that is not positive definite refuses the step);  V* = L L^t by Cholesky, Yv = V*^-1 W^t, z = V*^-1 g_x;
+ *      S = sum (Jc^t Jc, damped) - W Yv  (15 sums), rhs = sum g_c - W z (5 sums);  S dc = -rhs by Cholesky;
+ *      dX = -(z + Yv dc) per point.  A pivot that is not > 0 in any V* or in S, or a dc that is not finite, refuses the step.
+ *   4. Candidate: R' = exp([w]x) R with w = dc[0..3): theta^2 = w.w; below 2^-26: a = 1 - theta^2 / 6, b = 1/2 - theta^2 / 24,
+ *      otherwise a = sin(theta) / theta, b = 2 sin^2(theta / 2) / theta^2; exp = I + a [w]x + b (w w^t - theta^2 I).
+ *      t' = normalize(t + dc[3] b1 + dc[4] b2);  X' = X + dX.
+ *   5. Accepted iff every participating point has X'_2 > 0 and (R'X' + t')_2 > 0 and the objective at the candidate is strictly
+ *      lower (a NaN never is).  Accepted: lambda = max(lambda / 10, 1e-15), and the run ends when (old - new) / old < 2^-40.
+ *      Refused: lambda = 10 lambda, and the run ends when lambda > 1e12.  At most max_iterations iterations.
+ *   6. Rounded once to f32: d_R, d_t; d_c2[r][c] = (K_r0 M_0c + K_r1 M_1c) + K_r2 M_2c with M = [R | t] in f64; (x, y, z, 1) in
+ *      the participating matches' slots of d_points4d.  Every other slot keeps its bits.
+ * An item is LEFT ALONE -- d_R, d_t and d_points4d keep their bits, d_c2 is the formula of 6 on the inputs, all written by the
+ * same kernel -- when there is no winner (d_best[b][0] < 0), when fewer than 8 matches participate, when t has an entry that is
+ * not finite or |t| = 0, when no step was accepted, or when an output entry is not finite.  None of this raises the error word.
+ * d_stats (may be NULL) [batch][4] f64: [0] participating matches; [1] their mean squared reprojection error under the inputs
+ * (the objective over twice the count); [2] the same under the outputs as written (the f32 values); [3] accepted steps.  For an
+ * item left alone [0] is the count that was found and [1..3] are NaN.
+ * Deterministic: no floating-point atomics; every sum (the 15 + 5 entries of the reduced system, the objective) is a strided
+ * partial sum per lane (256 lanes, lane l takes the matches i = l mod 256 in rising order), a butterfly inside the wave, then
+ * the four wave sums in wave order: a pair gives the same bits in every run, in any batch, at any position.  A point's f64
+ * coordinates stay in f64 between iterations (in LDS, or in a workspace of the context's grow-only arena when n is above 3200).
+ * Stream-ordered on the context; does not synchronise.  VSLAM_ERR_INVALID, before anything is queued, for a null pointer
+ * (d_stats excepted), batch <= 0, kp_stride <= 0, max_iterations outside 1 .. 64, gate_sq not finite or <= 0.                */
+int vslam_refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const int32_t *d_matches, const int32_t *d_best,
+                       int batch, int kp_stride, const float *h_K, float gate_sq, int max_iterations,
+                       float *d_R /* [batch][9] in/out */, float *d_t /* [batch][3] in/out */, float *d_c2 /* [batch][12] out */,
+                       float *d_points4d /* [batch][kp_stride][4] in/out */, double *d_stats /* [batch][4], may be NULL */);
 
 /* ------------------------------------------------------------------ k-d tree */
 /* Replaces construct_kdtree(frame_kdtree&, points), src/KDTree.cpp:107-143.  The tree is the

@@ -24,7 +24,7 @@ SYMBOLS = [
     "vslam_last_error", "vslam_ctx_workspace_bytes", "vslam_version", "vslam_brief_pattern_31", "vslam_dev_alloc", "vslam_dev_free", "vslam_copy_h2d",
     "vslam_copy_d2h", "vslam_debug_stream_copy", "vslam_debug_valu_calib", "vslam_prof_enable", "vslam_prof_reset", "vslam_prof_count", "vslam_prof_get",
     "vslam_match_knn2_ratio", "vslam_ransac_sets", "vslam_ransac_fundamental", "vslam_ransac_solve",
-    "vslam_ransac_evaluate", "vslam_refit_fundamental", "vslam_kdtree_build",
+    "vslam_ransac_evaluate", "vslam_refit_fundamental", "vslam_refine_pairs", "vslam_kdtree_build",
     "vslam_kdtree_radius", "vslam_kdtree_nearest", "vslam_kdtree_cell_table", "vslam_extract_features", "vslam_extract_features_grid", "vslam_triangulate_points", "vslam_frontend_pairs_pose", "vslam_pipeline_batches_redone", "vslam_corner_stats", "vslam_bgr2gray", "vslam_min_eigen",
     "vslam_good_features", "vslam_gaussian7", "vslam_orb_describe", "vslam_extract_Rt", "vslam_triangulate", "vslam_associate_map_points", "vslam_reprojection_filter",
     "vslam_match_features",
@@ -199,6 +199,7 @@ class Context:
     OPT_MATCH_FORM = 8
     OPT_TREE_FORK = 9
     OPT_POSE_REFIT = 10
+    OPT_POSE_REFINE = 11
 
     def set_option(self, option, value):
         self._check(self.lib.vslam_ctx_set_option(self.handle, C.c_int(option), C.c_int(int(value))))
@@ -328,6 +329,26 @@ class Context:
         self._check(self.lib.vslam_refit_fundamental(self.handle, _ptr(xy1), _ptr(xy2), _ptr(matches), _ptr(best), C.c_int(B),
                                                      C.c_int(K), _ptr(F), _ptr(out), _ptr(stats)))
         return out, stats
+
+    def refine_pairs(self, xy1, xy2, matches, best, K, R, t, points4d, gate_sq=16.0, max_iterations=20, want_stats=True):
+        """vslam_refine_pairs: two-view bundle adjustment of each pair's R (B, 9 or 3, 3), t (B, 3) and points4d (B, K, 4), IN
+        PLACE, over the inlier matches (B, K, 2) / best (B, 4); K: the 3 x 3 camera matrix (host).  Returns
+        (R, t, c2 (B, 12), points4d, stats (B, 4) f64 or None) -- R, t and points4d are the tensors passed in."""
+        import numpy as np
+        torch = self.torch
+        B, Kp, _ = xy1.shape
+        for x, dt, nm in ((xy1, torch.float32, "xy1"), (xy2, torch.float32, "xy2"), (matches, torch.int32, "matches"),
+                          (best, torch.int32, "best"), (R, torch.float32, "R"), (t, torch.float32, "t"),
+                          (points4d, torch.float32, "points4d")):
+            self._dev(x, dt, nm)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        c2 = torch.empty((B, 12), dtype=torch.float32, device=xy1.device)
+        stats = torch.empty((B, 4), dtype=torch.float64, device=xy1.device) if want_stats else None
+        self._ready()
+        self._check(self.lib.vslam_refine_pairs(self.handle, _ptr(xy1), _ptr(xy2), _ptr(matches), _ptr(best), C.c_int(B), C.c_int(Kp),
+                                                Kh.ctypes.data_as(C.c_void_p), C.c_float(gate_sq), C.c_int(max_iterations),
+                                                _ptr(R), _ptr(t), _ptr(c2), _ptr(points4d), _ptr(stats)))
+        return R, t, c2, points4d, stats
 
     def kdtree_build(self, xy, n):
         torch = self.torch

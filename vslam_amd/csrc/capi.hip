@@ -420,6 +420,11 @@ int vslam_ctx_set_option(vslam_ctx *ctx, int option, int value) {
         ctx->pose_refit = value != 0;
         return VSLAM_OK;
     }
+    if (option == VSLAM_OPT_POSE_REFINE) {
+        VS_REQUIRE(ctx, value == 0 || value == 1, VSLAM_ERR_INVALID);
+        ctx->pose_refine = value != 0;
+        return VSLAM_OK;
+    }
     if (option == VSLAM_OPT_TREE_FORK) {
         VS_REQUIRE(ctx, value >= -1 && value <= 5, VSLAM_ERR_INVALID);
         ctx->tree_fork = value;
@@ -935,6 +940,10 @@ int vslam_frontend_pairs_pose(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, i
         if ((rc = vs_launch_refit(ctx, xy1, xy2, d_matches, d_best, pairs, kp_stride, d_F, d_F, nullptr))) return rc;
     if ((rc = vs_launch_extract_Rt(ctx, d_F, d_best, pairs, h_K, pose->d_R, pose->d_t, pose->d_c2))) return rc;
     if ((rc = vs_launch_triangulate(ctx, xy1, xy2, d_matches, d_best, pairs, kp_stride, h_K, pose->d_c2, pose->d_points4d))) return rc;
+    if (ctx->pose_refine)   // VSLAM_OPT_POSE_REFINE: the filter, and the caller, get the adjusted pose and points
+        if ((rc = vs_launch_refine_pairs(ctx, xy1, xy2, d_matches, d_best, pairs, kp_stride, h_K, 4.f * reproj_threshold_sq,
+                                         kVsPoseRefineIterations, pose->d_R, pose->d_t, pose->d_c2, pose->d_points4d, nullptr)))
+            return rc;
     return vs_launch_reproj_filter(ctx, pose->d_points4d, xy1, xy2, d_matches, d_best, pairs, kp_stride, h_K, pose->d_c2,
                                    d_map_point_ids, reproj_threshold_sq, pose->d_inlier_idx, pose->d_n_inliers, pose->d_error);
 }

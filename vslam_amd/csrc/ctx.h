@@ -58,6 +58,7 @@ struct vslam_ctx {
     int corner_window_pct = 135;                // VSLAM_OPT_CORNER_WINDOW_PCT
     int corner_list_cap = 0;                    // VSLAM_OPT_CORNER_LIST_CAP: 0 = 16 x max_corners + 4096, -1 = whole image
     bool pose_refit = false;        // VSLAM_OPT_POSE_REFIT: the pose chain and the tracking loop refit F over its inliers (refit.hip)
+    bool pose_refine = false;       // VSLAM_OPT_POSE_REFINE: two-view bundle adjustment of each pair's pose and points (refine.hip)
     bool ransac_all_sums = false;   // VSLAM_OPT_RANSAC_ALL_SUMS: exact residual sum of every hypothesis (ransac_score_kernel)
     // where the corner detector's last batch left its per-frame counters (vslam_corner_stats reads them after a stream wait)
     const uint32_t *stat_counts = nullptr;
@@ -208,6 +209,11 @@ int vs_launch_ransac_evaluate(vslam_ctx *ctx, const float *xy1, const float *xy2
 // the winner refitted over its inliers (refit.hip); F_out may be F_in
 int vs_launch_refit(vslam_ctx *ctx, const float *xy1, const float *xy2, const int32_t *matches, const int32_t *best, int batch,
                     int kp_stride, const float *F_in, float *F_out, double *stats);
+// two-view bundle adjustment of R, t and the points, in place (refine.hip); c2 = K [R | t] of what it leaves in R and t
+int vs_launch_refine_pairs(vslam_ctx *ctx, const float *xy1, const float *xy2, const int32_t *matches, const int32_t *best, int batch,
+                           int kp_stride, const float *h_K, float gate_sq, int max_iterations, float *R, float *t, float *c2,
+                           float *points4d, double *stats);
+constexpr int kVsPoseRefineIterations = 20;   // what VSLAM_OPT_POSE_REFINE runs with; its gate is 4 x the filter's threshold_sq
 int vs_launch_kdtree_build(vslam_ctx *ctx, const float *xy, const int32_t *n, int batch, int kp_stride,
                            int32_t *nodes);
 int vs_launch_kdtree_radius(vslam_ctx *ctx, const int32_t *nodes, const float *xy, const int32_t *n,

@@ -483,6 +483,13 @@ int map_step(vslam_ctx *ctx, vslam_map *m, const float *xy_last, const uint8_t *
         map_begin_kernel<<<T, kMT, 0, ctx->stream>>>(d, best);
     }
     if ((rc = vs_launch_extract_Rt(ctx, F, best, T, h_K, m->R, m->t, m->c2))) return rc;
+    const bool refine = ctx->pose_refine;
+    if (refine) {   // VSLAM_OPT_POSE_REFINE: the pose entered into the map, association, the filter and the append see the adjusted values
+        if ((rc = vs_launch_triangulate(ctx, xy_last, xy_cur, matches, best, T, m->kp_stride, h_K, m->c2, m->points4d))) return rc;
+        if ((rc = vs_launch_refine_pairs(ctx, xy_last, xy_cur, matches, best, T, m->kp_stride, h_K, 4.f * reproj_threshold_sq,
+                                         kVsPoseRefineIterations, m->R, m->t, m->c2, m->points4d, nullptr)))
+            return rc;
+    }
     {
         VsProfScope ps(ctx, "map_pose_kernel");
         map_pose_kernel<<<vs_div_up(T, 64), 64, 0, ctx->stream>>>(d, T, fid, best, m->R, m->t);
@@ -509,7 +516,7 @@ int map_step(vslam_ctx *ctx, vslam_map *m, const float *xy_last, const uint8_t *
         VsProfScope ps(ctx, "map_assoc_push_kernel");
         map_assoc_push_kernel<<<T, kMT, 0, ctx->stream>>>(d, fid, desc_cur);
     }
-    if ((rc = vs_launch_triangulate(ctx, xy_last, xy_cur, matches, best, T, m->kp_stride, h_K, m->c2, m->points4d))) return rc;
+    if (!refine && (rc = vs_launch_triangulate(ctx, xy_last, xy_cur, matches, best, T, m->kp_stride, h_K, m->c2, m->points4d))) return rc;
     if ((rc = vs_launch_reproj_filter(ctx, m->points4d, xy_last, xy_cur, matches, best, T, m->kp_stride, h_K, m->c2, m->ids_work,
                                       reproj_threshold_sq, m->inlier_idx, m->n_inliers, m->error)))
         return rc;

@@ -27,6 +27,7 @@
 
 #include "../../include/vslam/Frame.h"
 #include "../../include/vslam/helpers.h"
+#include "../../include/vslam/optimizer.h"
 #ifdef VSLAM_HAVE_OPENCV
 #include <opencv2/imgproc.hpp>
 #endif
@@ -842,7 +843,69 @@ void refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, c
     const int rc = vslam_refit_fundamental(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, d_F, d_F, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_refit_fundamental: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
+                  int kp_stride, const cv::Mat &K, float gate_sq, int max_iterations, float *d_R, float *d_t, float *d_c2,
+                  float *d_points4d, f64 *d_stats) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("refine_pairs: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_refine_pairs(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, k, gate_sq, max_iterations, d_R, d_t,
+                                      d_c2, d_points4d, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_refine_pairs: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
+
+// -------------------------------------------------------------------------------------- optimizer.h
+void optimizer::optimize(const cv::Mat &K, float gate_sq, int max_iterations, f64 *stats) {
+    const size_t n = measurements.size();
+    if (initial_poses.size() != 2 || initial_poses[1].rows != 3 || initial_poses[1].cols != 4 || initial_poses[1].type() != CV_32FC1)
+        throw std::invalid_argument("optimizer: initial_poses must hold two 3 x 4 CV_32F matrices");
+    if (n == 0 || landmark_priors.rows != (int)n || landmark_priors.cols != 4 || landmark_priors.type() != CV_32FC1)
+        throw std::invalid_argument("optimizer: landmark_priors must be measurements.size() x 4 CV_32F");
+    Lock lk(g_mu);
+    // one item whose keypoint slots are the measurements themselves: match i = (i, i)
+    std::vector<float> xy1(2 * n), xy2(2 * n), pts(4 * n);
+    std::vector<int32_t> m(2 * n);
+    for (size_t i = 0; i < n; i++) {
+        xy1[2 * i] = measurements[i].first.x; xy1[2 * i + 1] = measurements[i].first.y;
+        xy2[2 * i] = measurements[i].second.x; xy2[2 * i + 1] = measurements[i].second.y;
+        m[2 * i] = m[2 * i + 1] = (int32_t)i;
+        std::memcpy(&pts[4 * i], landmark_priors.ptr<float>((int)i), sizeof(float) * 4);
+    }
+    float R[9], t[3];
+    for (int r = 0; r < 3; r++) {
+        std::memcpy(R + 3 * r, initial_poses[1].ptr<float>(r), sizeof(float) * 3);
+        t[r] = initial_poses[1].ptr<float>(r)[3];
+    }
+    const int32_t best[4] = {0, (int32_t)n, 0, (int32_t)n};
+    struct Dev {
+        std::vector<void *> p;
+        ~Dev() { for (void *q : p) vslam_dev_free(ctx(), q); }
+        void *get(size_t bytes, const void *src) {
+            void *d = nullptr;
+            check(vslam_dev_alloc(ctx(), bytes, &d), "dev_alloc");
+            p.push_back(d);
+            if (src) check(vslam_copy_h2d(ctx(), d, src, bytes), "copy_h2d");
+            return d;
+        }
+    } dev;
+    float *d_xy1 = (float *)dev.get(8 * n, xy1.data()), *d_xy2 = (float *)dev.get(8 * n, xy2.data());
+    int32_t *d_m = (int32_t *)dev.get(8 * n, m.data()), *d_best = (int32_t *)dev.get(16, best);
+    float *d_R = (float *)dev.get(36, R), *d_t = (float *)dev.get(12, t), *d_c2 = (float *)dev.get(48, nullptr);
+    float *d_pts = (float *)dev.get(16 * n, pts.data());
+    f64 *d_stats = stats ? (f64 *)dev.get(32, nullptr) : nullptr;
+    vslam::refine_pairs(ctx(), d_xy1, d_xy2, d_m, d_best, 1, (int)n, K, gate_sq, max_iterations, d_R, d_t, d_c2, d_pts, d_stats);
+    check(vslam_copy_d2h(ctx(), R, d_R, 36), "copy_d2h");
+    check(vslam_copy_d2h(ctx(), t, d_t, 12), "copy_d2h");
+    check(vslam_copy_d2h(ctx(), pts.data(), d_pts, 16 * n), "copy_d2h");
+    if (stats) check(vslam_copy_d2h(ctx(), stats, d_stats, 32), "copy_d2h");
+    for (int r = 0; r < 3; r++) {
+        std::memcpy(initial_poses[1].ptr<float>(r), R + 3 * r, sizeof(float) * 3);
+        initial_poses[1].ptr<float>(r)[3] = t[r];
+    }
+    for (size_t i = 0; i < n; i++) std::memcpy(landmark_priors.ptr<float>((int)i), &pts[4 * i], sizeof(float) * 4);
+}
 
 // -------------------------------------------------------------------------------------- Frame.h
 void initialize_frame(Frame &frame, const cv::Mat &image, long frame_id) {
