@@ -4,7 +4,11 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [output directory]
+    python examples/render_map.py [--world] [output directory]
+
+--world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
+reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
+and on the right the same points and frusta in one coordinate system (vslam_world_render), seen from the same viewpoint.
 """
 import os
 import sys
@@ -25,7 +29,9 @@ def write_ppm(path, bgr):
 
 
 def main():
-    out_dir = sys.argv[1] if len(sys.argv) > 1 else "render_map_out"
+    args = [a for a in sys.argv[1:] if a != "--world"]
+    with_world = "--world" in sys.argv[1:]
+    out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
     W, H = 640, 480                                              # of the view
@@ -36,6 +42,7 @@ def main():
     bgr = synth.sequences_torch(7, tracks, frames, width, height, dev)
     seeds = torch.arange(tracks * (frames - 1), dtype=torch.int32, device=dev).reshape(tracks, frames - 1).contiguous()
     pmap = capi.PointMap(ctx, tracks, frames, max_corners, map_capacity=frames * max_corners, obs_capacity=4 * frames * max_corners)
+    world = pmap.attach_world() if with_world else None
     # features and matches of every frame and consecutive pair, once (this also runs the whole loop; the map is then rebuilt
     # step by step below so that it can be looked at after every step)
     out = ctx.track_sequences(pmap, bgr, max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
@@ -55,20 +62,28 @@ def main():
         return full.view(tracks, frames, *a.shape[1:])[:, f - 1].contiguous()
     pmap.reset()
     images = torch.empty((tracks, H, W, 3), dtype=torch.uint8, device=dev)
+    world_images = torch.empty((tracks, H, W, 3), dtype=torch.uint8, device=dev) if with_world else None
     last = {k: per_frame(out[k], 0) for k in ("xy", "desc", "nodes", "n")}
     for f in range(1, frames):
         cur = {k: per_frame(out[k], f) for k in ("xy", "desc", "nodes", "n")}
         pair = {k: per_pair(out[k], f) for k in ("matches", "best", "F")}
         pmap.step(last, cur, pair, bgr[:, f].contiguous(), K)
         pmap.render(view, W, H, out=(images, None))              # stream-ordered behind the step: no wait in between
+        if with_world:
+            world.render(pmap, view, W, H, out=(world_images, None))
         ctx.synchronize()
-        host = images.cpu().numpy()
+        host = torch.cat([images, world_images], 2).cpu().numpy() if with_world else images.cpu().numpy()
         for t in range(tracks):
             write_ppm(os.path.join(out_dir, f"track{t}_step{f:02d}.ppm"), host[t])
         last = cur
     sizes = pmap.view()["sizes"]
-    print(f"{tracks * (frames - 1)} images of {W} x {H} in {out_dir}/; map points per track: {[int(s) for s in sizes]}")
+    print(f"{tracks * (frames - 1)} images of {host.shape[2]} x {H} in {out_dir}/; map points per track: {[int(s) for s in sizes]}")
+    if with_world:
+        v = world.view()
+        print("scale per pair, track 0:", [round(float(s), 4) for s in v["scale"][0, 1:]], "links:", v["links"][0, 1:].tolist())
     pmap.close()
+    if with_world:
+        world.close()
     ctx.close()
 
 

@@ -42,6 +42,14 @@ struct PointMap {   // reference: include/PointMap.h:10-21
     // R_t and pose from it.
     std::shared_ptr<vslam::DeviceMap> device;
     void sync_to_host();
+
+    // The world frame beside the map (vslam::map_attach_world; include/vslam_amd.h, "the world frame"), as of the last
+    // sync_to_host(): the map's points in the coordinates of frame 0 (size x 4 CV_32F rows (x, y, z, 1), row i = points row i
+    // lifted) and one camera -> world pose per recorded frame (4 x 4 CV_32F).  Empty without an attached world.
+    const cv::Mat &world_points() const { return world_points_; }
+    const std::vector<cv::Mat> &world_poses() const { return world_poses_; }
+    cv::Mat world_points_;
+    std::vector<cv::Mat> world_poses_;
 };
 
 // reference: include/PointMap.h:23, src/PointMap.cpp:3-34 -- on the host-side members, as the reference writes it (a caller
@@ -63,4 +71,7 @@ void map_create(PointMap &pm, int max_frames, int kp_stride, int map_capacity, i
 // An empty `fundamental` (RANSAC accepted nothing) leaves the map untouched, as vslam_map_step documents.
 void map_step(PointMap &pm, const std::vector<std::pair<int, int>> &matches, const cv::Mat &fundamental, const cv::Mat &K,
               float radius = 2.f, u32 dist_threshold = 64, float threshold_sq = 4.f);
+// Gives pm's device map a world frame (a vslam::World of its shape, include/vslam/World.h): every map_step from now on advances
+// it and lifts the new points; sync_to_host() fills world_points() / world_poses().  Before the first map_step.
+void map_attach_world(PointMap &pm, int min_links = 8);
 }  // namespace vslam

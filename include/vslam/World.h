@@ -1,0 +1,58 @@
+// The world frame of the resident map as a C++ object: a vslam_world (include/vslam_amd.h, "the world frame") with the
+// lifetime of the object.  The reference has nothing like it -- its map keeps every pair's points in the last frame's camera
+// coordinates and in the pair's own unit -- so this is no drop-in; it is what a consumer of include/vslam/*.h uses to get
+// camera -> world poses and points in one coordinate system per track.  Header-only over the C ABI; arrays are device pointers.
+// For the one-track PointMap of include/vslam/PointMap.h see vslam::map_attach_world there.
+#pragma once
+#include <stdexcept>
+#include <string>
+
+#include "../vslam_amd.h"
+
+namespace vslam {
+
+class World {
+public:
+    // Capacities are fixed here; nothing is allocated afterwards.  Destroy it before the context, and after a map it is
+    // attached to.  min_links: links a pair needs to set its own scale (otherwise it keeps the previous one).
+    World(vslam_ctx *ctx, int tracks, int max_frames, int kp_stride, int min_links = 8) : ctx_(ctx) {
+        check(vslam_world_create(ctx, tracks, max_frames, kp_stride, min_links, &world_), "vslam_world_create");
+    }
+    ~World() {
+        if (world_) vslam_world_destroy(world_);
+    }
+    World(const World &) = delete;
+    World &operator=(const World &) = delete;
+
+    void reset() { check(vslam_world_reset(ctx_, world_), "vslam_world_reset"); }
+    // one frame for every track, stream-ordered: [tracks][...] device arrays as vslam_world_step takes them
+    void step(const int32_t *d_matches, const int32_t *d_best, const float *d_points4d, const float *d_R, const float *d_t,
+              const int32_t *d_n_last, const int32_t *d_n_cur) {
+        check(vslam_world_step(ctx_, world_, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur), "vslam_world_step");
+    }
+    // rows [d_lo, d_hi) per track of the points of pair (frame - 1 -> frame) into d_out; other rows keep their bits
+    void lift(int frame, const float *d_points, int stride, const int32_t *d_lo, const int32_t *d_hi, float *d_out) {
+        check(vslam_world_lift(ctx_, world_, frame, d_points, stride, d_lo, d_hi, d_out), "vslam_world_lift");
+    }
+    vslam_world_arrays view() const {
+        vslam_world_arrays a;
+        check(vslam_world_view(world_, &a), "vslam_world_view");
+        return a;
+    }
+    void attach_to(vslam_map *map) { check(vslam_map_attach_world(map, world_), "vslam_map_attach_world"); }
+    void render(vslam_map *map, int track_lo, int track_count, const vslam_view &view, int width, int height, int row_stride,
+                uint8_t *d_bgr_out, float *d_depth_out = nullptr) {
+        check(vslam_world_render(ctx_, world_, map, track_lo, track_count, &view, width, height, row_stride, d_bgr_out, d_depth_out),
+              "vslam_world_render");
+    }
+    vslam_world *handle() const { return world_; }
+
+private:
+    void check(int rc, const char *what) const {
+        if (rc != VSLAM_OK) throw std::runtime_error(std::string(what) + ": " + vslam_last_error(ctx_));
+    }
+    vslam_ctx *ctx_ = nullptr;
+    vslam_world *world_ = nullptr;
+};
+
+}  // namespace vslam

@@ -615,6 +615,86 @@ int vslam_render_points(vslam_ctx *ctx, const float *d_points, const uint8_t *d_
 int vslam_map_render(vslam_ctx *ctx, vslam_map *map, int track_lo, int track_count, const vslam_view *h_view,
                      int width, int height, int row_stride, uint8_t *d_bgr_out, float *d_depth_out);
 
+/* ------------------------------------------------------------ the world frame (a second, opt-in view beside the map)
+ * The map above is the reference's, bit for bit: every pair's t has length 1 (extract_Rt), so every pair's points have a unit of
+ * their own; they are in the LAST frame's camera coordinates (c1 = [K | 0]); and `pose` chains last -> current transforms.  A
+ * vslam_world puts the same tracks into ONE coordinate system per track -- that of the track's frame 0, in the unit of its first
+ * pair with a model -- without touching what the map holds.  THIS TEXT and tests/ref_world.py are the contract.
+ *
+ * Per track and step (f - 1 -> f), from the step's R [9], t [3] (f32, as vslam_extract_Rt / vslam_refine_pairs leave them), the
+ * compacted inlier matches m = 0 .. n - 1, n = d_best[.][3] clamped to 0 .. kp_stride, and their triangulated points X_m
+ * (d_points4d slot m; the fourth entry is not read).  ALL arithmetic is f64, never fused, sums left to right; f32 inputs are
+ * widened first.  |v|^2 = (x x + y y) + z z.
+ *   carry   [kp_stride] per track: an f64 3-vector and a validity per keypoint of the LAST frame: that keypoint's point in the
+ *           last frame's camera coordinates, in world units, as the previous step left it.
+ *   in range: 0 <= first < min(d_n_last, kp_stride) and 0 <= second < min(d_n_cur, kp_stride); any other match is ignored.
+ *   usable: Y_m = R X_m + t, row r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r; X_m and Y_m finite, X_m.z > 0 and Y_m.z > 0.
+ *   link:   in range, usable, carry[first] valid, and q = |carry[first]|^2 / |X_m|^2 finite (it is unless a square overflows
+ *           or |X_m|^2 underflows to 0; such a match still carries on, it does not vote).
+ *   scale:  with L links and L >= min_links, s_f = sqrt(q_(k)), the element of rank k = (L - 1) / 2 (integer division) among the
+ *           q in ascending order -- a value, so arrival order cannot show.  Otherwise s_f = s_(f-1); s_0 = 1.  d_links[.][f] = L.
+ *   pose:   camera -> world.  Twc_0 = I;  Twc_f = Twc_(f-1) * [R^t | -(s_f (R^t t))] with (R^t t)_i = ((R_0i t_0 + R_1i t_1) +
+ *           R_2i t_2); the 4 x 4 product is P_rc = ((A_r0 B_0c + A_r1 B_1c) + A_r2 B_2c) + A_r3 B_3c, all four terms, row 3
+ *           included.  NOTHING IS RE-ORTHONORMALISED: the rotation block is a product of f32-rounded rotations and drifts from
+ *           orthogonality by about 2^-24 per frame.
+ *   lift:   a point X of this pair becomes xf(Twc_(f-1), (s_f x, s_f y, s_f z)) rounded once to f32, w = 1 (xf as for the
+ *           renderer above).
+ *   new carry: keyed by `second`: s_f Y_m for every in-range usable match; of two matches onto one `second` the HIGHER match
+ *           index wins; every other entry is invalid.
+ *   a pair without a winner (d_best[.][0] < 0): Twc_f = Twc_(f-1), s_f = s_(f-1), d_links = -1, the carry all invalid.
+ * The f64 square root is the device library's, which is correctly rounded on gfx950 (tests/test_gpu_world.py holds it to the
+ * host's on thousands of values), so every output is held bit for bit.  The selection is a radix select over the u64 bit patterns
+ * (non-negative doubles order as their bits) with integer histograms in LDS: no sort, no floating-point atomics, the same bits in
+ * every batch slot and run.
+ *
+ * A world belongs to the context it was made on and is destroyed before it; capacities are fixed at creation and
+ * vslam_world_reset / _step / _lift / _view / _render allocate nothing (vslam_map_attach_world allocates d_world_points, once).
+ * Every call is stream-ordered on the context and does not synchronise.  kp_stride <= VSLAM_MAX_KP (VSLAM_ERR_CAPACITY),
+ * min_links >= 1 (8 is the default of the Python and C++ surfaces).                                                          */
+typedef struct vslam_world vslam_world;
+typedef struct vslam_world_arrays {
+    int32_t tracks, max_frames, kp_stride, min_links;
+    int32_t map_capacity;            /* 0 until attached to a map                                                     */
+    int32_t frames;                  /* frames recorded so far, frame 0 included (host-side counter)                  */
+    double *d_Twc;                   /* [tracks][max_frames][16] camera -> world, row-major 4 x 4                     */
+    float *d_pose;                   /* [tracks][max_frames][16] the same rounded once: what vslam_render_points takes */
+    double *d_scale;                 /* [tracks][max_frames]                                                           */
+    int32_t *d_links;                /* [tracks][max_frames] L; -1: no winner; 0 for frame 0                           */
+    double *d_carry;                 /* [tracks][kp_stride][3]                                                         */
+    int32_t *d_carry_index;          /* [tracks][kp_stride] the match that wrote the entry, -1 = invalid               */
+    float *d_world_points;           /* [tracks][map_capacity][4], NULL until attached                                 */
+} vslam_world_arrays;
+int vslam_world_create(vslam_ctx *ctx, int tracks, int max_frames, int kp_stride, int min_links, vslam_world **out);
+/* Waits for the context's stream.  A world that is attached to a map is destroyed after that map, or detached first. */
+int vslam_world_destroy(vslam_world *world);
+/* Back to frame 0: identity poses, scale 1, links 0, no carry, d_world_points zero. */
+int vslam_world_reset(vslam_ctx *ctx, vslam_world *world);
+/* Advances every track by one frame ([tracks][...] batches: d_matches [.][kp_stride][2], d_best [.][4], d_points4d
+ * [.][kp_stride][4], d_R [.][9], d_t [.][3], d_n_last / d_n_cur [.]).  d_matches is 8-byte and d_points4d 16-byte aligned.
+ * A step beyond max_frames does nothing and raises the context's sticky error word, as vslam_map_step does.              */
+int vslam_world_step(vslam_ctx *ctx, vslam_world *world, const int32_t *d_matches, const int32_t *d_best,
+                     const float *d_points4d, const float *d_R, const float *d_t, const int32_t *d_n_last,
+                     const int32_t *d_n_cur);
+/* Lifts rows [d_lo[track], d_hi[track]) (clamped to 0 .. stride) of d_points [tracks][stride][4], points of pair
+ * (frame - 1 -> frame), 1 <= frame < frames recorded, into d_out [tracks][stride][4]; rows outside the range keep their bits.
+ * d_out may be d_points.  Both are 16-byte aligned.                                                                        */
+int vslam_world_lift(vslam_ctx *ctx, vslam_world *world, int frame, const float *d_points, int stride, const int32_t *d_lo,
+                     const int32_t *d_hi, float *d_out);
+int vslam_world_view(vslam_world *world, vslam_world_arrays *out);
+/* From now on vslam_map_step and vslam_track_sequences run the world step behind each map step, on the step's own R, t and
+ * points4d (the adjusted ones under VSLAM_OPT_POSE_REFINE), and lift the points appended in that step -- rows [size before, size
+ * after) of d_points -- into d_world_points.  A track the map leaves untouched for a step (capacity, or no winner) appends
+ * nothing; its world still advances as specified.  vslam_map_reset resets the world too.  tracks, max_frames, kp_stride and the
+ * frames recorded so far must agree and both must belong to one context (VSLAM_ERR_INVALID otherwise).  world = NULL detaches.
+ * Without an attached world no launch is added to a map step and every output of the map keeps its bits; with one, the map's own
+ * arrays keep their bits as well.                                                                                           */
+int vslam_map_attach_world(vslam_map *map, vslam_world *world);
+/* vslam_render_points over d_world_points, the map's colours and sizes and the world's f32 poses, for the frames recorded so
+ * far; `map` is the map the world is attached to.  Arguments as for vslam_map_render.                                      */
+int vslam_world_render(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int track_lo, int track_count,
+                       const vslam_view *h_view, int width, int height, int row_stride, uint8_t *d_bgr_out,
+                       float *d_depth_out);
+
 /* ------------------------------------------------------------------ pipeline */
 /* match_features(frame1, frame2, rf, matches, F), src/Frame.cpp:82-105, for a batch of pairs
  * whose features are already on the device: match -> sets -> RANSAC -> inlier matches.

@@ -30,6 +30,8 @@ SYMBOLS = [
     "vslam_match_features",
     "vslam_map_create", "vslam_map_destroy", "vslam_map_reset", "vslam_map_step", "vslam_map_view", "vslam_map_observations",
     "vslam_track_sequences",
+    "vslam_world_create", "vslam_world_destroy", "vslam_world_reset", "vslam_world_step", "vslam_world_lift", "vslam_world_view",
+    "vslam_map_attach_world", "vslam_world_render",
     "vslam_view_default", "vslam_view_look_at", "vslam_render_points", "vslam_map_render",
     "vslam_frontend_pairs", "vslam_frontend_sequence", "vslam_pack_records",
     "vslam_host_alloc", "vslam_host_free", "vslam_upload_async", "vslam_upload_fence", "vslam_upload_wait", "vslam_download_async",
@@ -56,6 +58,13 @@ class MapArrays(C.Structure):   # vslam_map_arrays
                 ("obs_capacity", C.c_int32), ("frames", C.c_int32), ("d_points", C.c_void_p), ("d_colors", C.c_void_p),
                 ("d_sizes", C.c_void_p), ("d_map_point_ids", C.c_void_p), ("d_R_t", C.c_void_p), ("d_pose", C.c_void_p),
                 ("d_obs_counts", C.c_void_p), ("d_n_obs", C.c_void_p)]
+
+
+class WorldArrays(C.Structure):   # vslam_world_arrays
+    _fields_ = [("tracks", C.c_int32), ("max_frames", C.c_int32), ("kp_stride", C.c_int32), ("min_links", C.c_int32),
+                ("map_capacity", C.c_int32), ("frames", C.c_int32), ("d_Twc", C.c_void_p), ("d_pose", C.c_void_p),
+                ("d_scale", C.c_void_p), ("d_links", C.c_void_p), ("d_carry", C.c_void_p), ("d_carry_index", C.c_void_p),
+                ("d_world_points", C.c_void_p)]
 
 
 class VslamError(RuntimeError):
@@ -724,6 +733,7 @@ class PointMap:
         self.lib = ctx.lib
         self.tracks, self.max_frames, self.kp_stride = tracks, max_frames, kp_stride
         self.map_capacity, self.obs_capacity = map_capacity, obs_capacity
+        self.world = None
         self.handle = C.c_void_p()
         ctx._check(self.lib.vslam_map_create(ctx.handle, C.c_int(tracks), C.c_int(max_frames), C.c_int(kp_stride),
                                              C.c_int(map_capacity), C.c_int(obs_capacity), C.byref(self.handle)))
@@ -753,6 +763,20 @@ class PointMap:
             C.c_int(W), C.c_int(H), C.c_int(row_bytes), Kh.ctypes.data_as(C.c_void_p), C.c_float(radius),
             C.c_uint32(dist_threshold), C.c_float(thr_sq)))
 
+    def attach_world(self, world=None, min_links=8):
+        """vslam_map_attach_world: from now on step() / track_sequences advance `world` (a new World of this map's shape when
+        none is given) behind every map step and lift the appended points into its world_points; view() then carries the
+        world's arrays as well.  Returns the world; it is closed after this map, or detached first (detach_world())."""
+        if world is None:
+            world = World(self.ctx, self.tracks, self.max_frames, self.kp_stride, min_links)
+        self.ctx._check(self.lib.vslam_map_attach_world(self.handle, world.handle))
+        self.world = world
+        return world
+
+    def detach_world(self):
+        self.ctx._check(self.lib.vslam_map_attach_world(self.handle, C.c_void_p(0)))
+        self.world = None
+
     def arrays(self):
         a = MapArrays()
         self.ctx._check(self.lib.vslam_map_view(self.handle, C.byref(a)))
@@ -769,10 +793,13 @@ class PointMap:
             h = np.empty(shape, dtype)
             self.ctx._check(self.lib.vslam_copy_d2h(self.ctx.handle, h.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(h.nbytes)))
             return h
-        return dict(frames=int(a.frames), points=get(a.d_points, (T, M, 4), np.float32), colors=get(a.d_colors, (T, M, 3), np.uint8),
-                    sizes=get(a.d_sizes, (T,), np.int32), map_point_ids=get(a.d_map_point_ids, (T, Fr, Kp), np.int32),
-                    R_t=get(a.d_R_t, (T, Fr, 16), np.float32), pose=get(a.d_pose, (T, Fr, 16), np.float32),
-                    obs_counts=get(a.d_obs_counts, (T, M), np.int32), n_obs=get(a.d_n_obs, (T,), np.int32))
+        v = dict(frames=int(a.frames), points=get(a.d_points, (T, M, 4), np.float32), colors=get(a.d_colors, (T, M, 3), np.uint8),
+                 sizes=get(a.d_sizes, (T,), np.int32), map_point_ids=get(a.d_map_point_ids, (T, Fr, Kp), np.int32),
+                 R_t=get(a.d_R_t, (T, Fr, 16), np.float32), pose=get(a.d_pose, (T, Fr, 16), np.float32),
+                 obs_counts=get(a.d_obs_counts, (T, M), np.int32), n_obs=get(a.d_n_obs, (T,), np.int32))
+        if self.world is not None:   # the world frame beside it, under world_* names
+            v.update({"world_" + k: x for k, x in self.world.view().items()})
+        return v
 
     def render(self, view, width, height, tracks=None, depth=False, row_stride=None, out=None):
         """vslam_map_render: the map as images on the device, one per track -- all of them, or tracks = (lo, count).  Returns
@@ -802,6 +829,86 @@ class PointMap:
         if self.handle:
             if self.ctx.handle:
                 self.lib.vslam_map_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class World:
+    """A vslam_world: camera -> world poses, per-pair scales and the per-keypoint carry of `tracks` sequences in one coordinate
+    system per track (include/vslam_amd.h, "the world frame"; tests/ref_world.py).  Stepped by hand with step() / lift(), or
+    attached to a PointMap (PointMap.attach_world), which then steps it and fills world_points."""
+
+    def __init__(self, ctx, tracks, max_frames, kp_stride, min_links=8):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.tracks, self.max_frames, self.kp_stride, self.min_links = tracks, max_frames, kp_stride, min_links
+        self.handle = C.c_void_p()
+        ctx._check(self.lib.vslam_world_create(ctx.handle, C.c_int(tracks), C.c_int(max_frames), C.c_int(kp_stride),
+                                               C.c_int(min_links), C.byref(self.handle)))
+
+    def reset(self):
+        self.ctx._check(self.lib.vslam_world_reset(self.ctx.handle, self.handle))
+
+    def step(self, matches, best, points4d, R, t, n_last, n_cur):
+        """vslam_world_step: matches (T, K, 2) i32, best (T, 4) i32, points4d (T, K, 4) f32, R (T, 9) f32, t (T, 3) f32,
+        n_last / n_cur (T,) i32 -- cuda tensors (None is passed on as a null pointer)."""
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_step(self.ctx.handle, self.handle, _ptr(matches), _ptr(best), _ptr(points4d), _ptr(R),
+                                                  _ptr(t), _ptr(n_last), _ptr(n_cur)))
+
+    def lift(self, frame, points, lo, hi, out=None):
+        """vslam_world_lift: rows [lo[t], hi[t]) of points (T, N, 4) f32, points of pair (frame - 1 -> frame), into `out` (a new
+        zero tensor when none is given); other rows keep their bits."""
+        if out is None:
+            out = self.ctx.torch.zeros_like(points)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_lift(self.ctx.handle, self.handle, C.c_int(frame), _ptr(points),
+                                                  C.c_int(points.shape[1] if points is not None else 0), _ptr(lo), _ptr(hi),
+                                                  _ptr(out)))
+        return out
+
+    def arrays(self):
+        a = WorldArrays()
+        self.ctx._check(self.lib.vslam_world_view(self.handle, C.byref(a)))
+        return a
+
+    def view(self):
+        """Host copies (numpy) of the state, after waiting for the context's stream (the error word is left alone)."""
+        import numpy as np
+        a = self.arrays()
+        self.ctx._check(self.lib.vslam_ctx_wait(self.ctx.handle))
+        T, Fr, Kp = self.tracks, self.max_frames, self.kp_stride
+
+        def get(ptr, shape, dtype):
+            h = np.empty(shape, dtype)
+            self.ctx._check(self.lib.vslam_copy_d2h(self.ctx.handle, h.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(h.nbytes)))
+            return h
+        v = dict(frames=int(a.frames), Twc=get(a.d_Twc, (T, Fr, 16), np.float64), pose=get(a.d_pose, (T, Fr, 16), np.float32),
+                 scale=get(a.d_scale, (T, Fr), np.float64), links=get(a.d_links, (T, Fr), np.int32),
+                 carry=get(a.d_carry, (T, Kp, 3), np.float64), carry_index=get(a.d_carry_index, (T, Kp), np.int32))
+        if a.d_world_points:
+            v["points"] = get(a.d_world_points, (T, int(a.map_capacity), 4), np.float32)
+        return v
+
+    def render(self, pmap, view, width, height, tracks=None, depth=False, row_stride=None, out=None):
+        """vslam_world_render: PointMap.render's images in the world frame (world_points, the map's colours, the world's poses)."""
+        lo, count = (0, self.tracks) if tracks is None else tracks
+        bgr, dep = self.ctx._render_outputs(max(count, 0), width, height, depth, row_stride, out)
+        self.ctx._check(self.lib.vslam_world_render(self.ctx.handle, self.handle, pmap.handle, C.c_int(lo), C.c_int(count),
+                                                    C.byref(view), C.c_int(width), C.c_int(height),
+                                                    C.c_int(row_stride or 3 * width), _ptr(bgr), _ptr(dep)))
+        return (bgr, dep) if depth else bgr
+
+    def close(self):
+        """After the map it is attached to and before the context's close()."""
+        if self.handle:
+            if self.ctx.handle:
+                self.lib.vslam_world_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -308,3 +308,27 @@ int vs_launch_reproj_filter(vslam_ctx *ctx, const float *points4d, const float *
                             const int32_t *best, int batch, int kp_stride, const float *h_K, const float *c2,
                             const int32_t *map_point_ids, float threshold_sq, int32_t *out_idx, int32_t *out_n,
                             double *out_err);
+
+// ---- the world frame (world.hip); map.hip drives it behind a map step when one is attached ----
+struct vslam_world {
+    vslam_ctx *ctx = nullptr;
+    int tracks = 0, max_frames = 0, kp_stride = 0, min_links = 0;
+    int frames = 1;
+    double *Twc = nullptr;          // [tracks][max_frames][16]
+    float *pose = nullptr;          // [tracks][max_frames][16]
+    double *scale = nullptr;        // [tracks][max_frames]
+    int32_t *links = nullptr;       // [tracks][max_frames]
+    double *carry = nullptr;        // [tracks][kp_stride][3]
+    int32_t *carry_idx = nullptr;   // [tracks][kp_stride]
+    // made by vs_world_bind when a map takes the world on
+    int map_capacity = 0;
+    float *world_points = nullptr;  // [tracks][map_capacity][4]
+    int32_t *size_before = nullptr; // [tracks] the map's sizes ahead of the step
+    std::vector<void *> owned;
+};
+int vs_world_bind(vslam_ctx *ctx, vslam_world *w, int map_capacity);
+// around one map step: the sizes ahead of it; then the world step and the lift of rows [size before, size after)
+int vs_world_before_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *sizes);
+int vs_world_after_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *matches, const int32_t *best, const float *points4d,
+                            const float *R, const float *t, const int32_t *n_last, const int32_t *n_cur, const float *map_points,
+                            const int32_t *sizes);

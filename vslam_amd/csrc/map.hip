@@ -50,6 +50,7 @@ struct vslam_map {
     int32_t *st_n[2] = {nullptr, nullptr};
     int32_t *st_nodes = nullptr, *st_matches = nullptr, *st_best = nullptr;
     float *st_F = nullptr;
+    vslam_world *world = nullptr;   // vslam_map_attach_world: stepped and reset with the map
     std::vector<void *> owned;
 };
 
@@ -478,6 +479,7 @@ int map_step(vslam_ctx *ctx, vslam_map *m, const float *xy_last, const uint8_t *
     }
     const int T = m->tracks, fid = m->frames;
     const MapDev d = dev_of(m);
+    if (m->world && (rc = vs_world_before_map_step(ctx, m->world, m->sizes))) return rc;
     {
         VsProfScope ps(ctx, "map_begin_kernel");
         map_begin_kernel<<<T, kMT, 0, ctx->stream>>>(d, best);
@@ -527,6 +529,10 @@ int map_step(vslam_ctx *ctx, vslam_map *m, const float *xy_last, const uint8_t *
     }
     VS_HIP(ctx, hipGetLastError());
     m->frames = fid + 1;
+    // the world frame follows on the step's own R, t and points4d; the rows appended above are lifted
+    if (m->world && (rc = vs_world_after_map_step(ctx, m->world, matches, best, m->points4d, m->R, m->t, n_last, n_cur, m->points,
+                                                  m->sizes)))
+        return rc;
     return VSLAM_OK;
 }
 
@@ -557,6 +563,24 @@ int vslam_map_reset(vslam_ctx *ctx, vslam_map *map) {
     map_reset_kernel<<<dim3(blocks, map->tracks), kMT, 0, ctx->stream>>>(dev_of(map));
     VS_HIP(ctx, hipGetLastError());
     map->frames = 1;
+    if (map->world) return vslam_world_reset(ctx, map->world);
+    return VSLAM_OK;
+}
+
+int vslam_map_attach_world(vslam_map *map, vslam_world *world) {
+    if (!map || !map->ctx) return VSLAM_ERR_INVALID;
+    vslam_ctx *ctx = map->ctx;
+    if (!world) {
+        map->world = nullptr;
+        return VSLAM_OK;
+    }
+    VS_REQUIRE(ctx, world->ctx == ctx, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, world->tracks == map->tracks && world->max_frames == map->max_frames && world->kp_stride == map->kp_stride,
+               VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, world->frames == map->frames, VSLAM_ERR_INVALID);
+    const int rc = vs_world_bind(ctx, world, map->map_capacity);
+    if (rc != VSLAM_OK) return rc;
+    map->world = world;
     return VSLAM_OK;
 }
 

@@ -3,6 +3,7 @@
 #include <stdexcept>
 
 #include "../../include/vslam/PointMap.h"
+#include "../../include/vslam/World.h"
 #include "host_internal.h"
 
 using vslam::detail::check;
@@ -11,6 +12,7 @@ using vslam::detail::context;
 namespace vslam {
 struct DeviceMap {
     vslam_map *map = nullptr;
+    std::unique_ptr<World> world;   // vslam::map_attach_world; destroyed after the map
     int max_frames = 0, kp_stride = 0, map_capacity = 0, obs_capacity = 0;
     int recorded = 0;   // id of the last frame stepped (0: only the first frame so far)
     // one frame step's inputs: features of two frames (ping-pong), the pair's outputs, the image
@@ -33,6 +35,7 @@ struct DeviceMap {
     }
     ~DeviceMap() {
         if (map) vslam_map_destroy(map);
+        world.reset();
         for (void *d : owned) vslam_dev_free(context(), d);
         if (image) vslam_dev_free(context(), image);
     }
@@ -130,6 +133,14 @@ void map_step(PointMap &pm, const std::vector<std::pair<int, int>> &matches, con
     check(vslam_ctx_synchronize(context()), "PointMap: map_step (a capacity of the map, or more than 16 acceptable hits)");
 }
 
+void map_attach_world(PointMap &pm, int min_links) {
+    if (!pm.device) throw std::logic_error("PointMap: vslam::map_create first");
+    DeviceMap &d = *pm.device;
+    if (d.world) throw std::logic_error("PointMap: a world is attached already");
+    d.world.reset(new World(context(), 1, d.max_frames, d.kp_stride, min_links));
+    d.world->attach_to(d.map);
+}
+
 namespace detail {
 vslam_map *device_map(PointMap &pm) {
     if (!pm.device) throw std::logic_error("PointMap: vslam::map_create first");
@@ -183,6 +194,18 @@ void PointMap::sync_to_host() {
         frm.pose.create(4, 4, CV_32FC1);
         check(vslam_copy_d2h(context(), frm.R_t.ptr<float>(0), a.d_R_t + (size_t)f * 16, sizeof(float) * 16), "copy_d2h");
         check(vslam_copy_d2h(context(), frm.pose.ptr<float>(0), a.d_pose + (size_t)f * 16, sizeof(float) * 16), "copy_d2h");
+    }
+    world_points_ = cv::Mat();
+    world_poses_.clear();
+    if (d.world) {
+        const vslam_world_arrays w = d.world->view();
+        world_points_.create(sz, 4, CV_32FC1);
+        if (sz > 0) check(vslam_copy_d2h(context(), world_points_.ptr<float>(0), w.d_world_points, sizeof(float) * 4 * (size_t)sz), "copy_d2h");
+        for (int f = 0; f < std::min<int>(w.frames, w.max_frames); f++) {
+            cv::Mat pose4(4, 4, CV_32FC1);
+            check(vslam_copy_d2h(context(), pose4.ptr<float>(0), w.d_pose + (size_t)f * 16, sizeof(float) * 16), "copy_d2h");
+            world_poses_.push_back(pose4);
+        }
     }
 }
 
