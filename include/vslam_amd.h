@@ -316,8 +316,11 @@ int vslam_refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, c
  * reference's pre-order node array reduced to its pt_index column: d_nodes [batch][kp_stride].
  * Child positions are implicit (left subtree len/2 nodes, right len - len/2 - 1).  Tie placement
  * reproduces libstdc++'s std::nth_element (introselect) exactly.  A tree is built in one workgroup's
- * LDS (20 bytes per slot): kp_stride <= 8160, VSLAM_ERR_CAPACITY beyond — which is also the limit of
+ * LDS, 14 bytes per slot (two float coordinates, a 16-bit index, two 16-bit partition lists) and 4 more,
+ * rounded up to 16, within 160 KB less 512 bytes: 14 * kp_stride + 4 <= 163328, that is
+ * kp_stride <= VSLAM_KDTREE_MAX_KP = 11666, VSLAM_ERR_CAPACITY beyond — which is also the limit of
  * vslam_extract_features / vslam_frontend_* when they are asked for the trees (d_nodes != NULL).  */
+#define VSLAM_KDTREE_MAX_KP 11666
 int vslam_kdtree_build(vslam_ctx *ctx, const float *d_xy, const int32_t *d_n, int batch,
                        int kp_stride, int32_t *d_nodes);
 /* Replaces radius_search(frame_kdtree, points, query, radius), src/KDTree.cpp:145-171.
@@ -518,7 +521,7 @@ int vslam_map_observations(vslam_ctx *ctx, vslam_map *map, int32_t *d_offsets, i
  * straddle two tracks are computed and ignored (1 / frames of the matching time) -- then frames - 1 map steps.  Per-frame
  * outputs [tracks * frames] slots and per-pair outputs [tracks * frames - 1] slots are the caller's, as in
  * vslam_frontend_sequence with frames = tracks * frames: pair (track, f -> f + 1) is slot track * frames + f, so the records
- * path keeps working.  kp_stride is the map's (<= 8160: the trees are needed).  Steps beyond max_frames do nothing and raise the
+ * path keeps working.  kp_stride is the map's (<= VSLAM_KDTREE_MAX_KP: the trees are needed).  Steps beyond max_frames do nothing and raise the
  * error word, like vslam_map_step.                                                                                        */
 int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, int frames, int width, int height,
                           int row_stride, const vslam_extract_params *params, const uint32_t *d_seeds, int hyp, float threshold,

@@ -400,13 +400,16 @@ def case(seed, Kp, n, sigma=0.5):
 
 GATE_SQ = 16.0           # 4 x the pose chain's reproj_threshold_sq of 4
 MAX_ITERATIONS = 20
-COMPARISON_SHAPES = [(64, 8), (64, 9), (64, 63), (64, 64), (1024, 255), (1024, 256), (1024, 257), (1024, 1023), (8160, 8160)]
+COMPARISON_SHAPES = [(64, 8), (64, 9), (64, 63), (64, 64), (1024, 255), (1024, 256), (1024, 257), (1024, 1023), (8160, 8160),
+                     (4096, 3200), (4096, 3201)]   # the last pair whose point state the device keeps in LDS, the first it does not
 MIXED_BATCH = (1024, [300, 8, 1023, 77, 256, 511, 40])
+SEAM_BATCH = (4096, [3200, 64, 3201])   # one launch: the two sides of that seam and a small pair (the first and the last shapes
+                                        # are the comparison shapes above, the same inputs)
 # Seeds per input, chosen on the CPU (tests/test_ref_refine.py checks what they were chosen for): the reference's extract_Rt may
 # pick an (R, t) that puts the points behind a camera -- a legitimate "left alone" input, no comparison -- so each seed is the
 # first from its starting value at which at least n - 2 matches participate and the refinement is comparable.
 SHAPE_SEEDS = {(64, 8): 130, (64, 9): 168, (64, 63): 238, (64, 64): 304, (1024, 255): 359, (1024, 256): 424, (1024, 257): 488,
-               (1024, 1023): 555, (8160, 8160): 612}
+               (1024, 1023): 555, (8160, 8160): 612, (4096, 3200): 702, (4096, 3201): 770, (4096, 64): 840}
 MIXED_SEEDS = {0: 1003, 1: 1070, 2: 1130, 3: 1199, 4: 1257, 5: 1327, 6: 1384}
 
 
@@ -429,6 +432,10 @@ def comparison_cases():
     Kp, ns = MIXED_BATCH
     for j, n in enumerate(ns):
         out.append((f"mixed{j}_n{n}",) + case(MIXED_SEEDS[j], Kp, n))
+    Kp, ns = SEAM_BATCH
+    for n in ns:
+        if (Kp, n) not in COMPARISON_SHAPES:
+            out.append((f"K{Kp}_n{n}",) + case(SHAPE_SEEDS[(Kp, n)], Kp, n))
     return out
 
 

@@ -103,6 +103,8 @@ def test_refine_matches_reference(ctx, refs, K, n):
     name = f"K{K}_n{n}"
     out = run(ctx, *stack([cases[name]]))
     hold_to_reference(name, [o[0] for o in out], res[name], cases[name][1:], delta)
+    if n in (3200, 3201):
+        assert n - 2 <= out[4][0, 0] <= n, (name, out[4][0])
 
 
 def test_refine_mixed_batch_matches_reference(ctx, refs):
@@ -112,6 +114,18 @@ def test_refine_mixed_batch_matches_reference(ctx, refs):
     out = run(ctx, *stack([cases[k] for k in names]))
     for b, name in enumerate(names):
         hold_to_reference(name, [o[b] for o in out], res[name], cases[name][1:], delta)
+
+
+def test_refine_lds_and_arena_pairs_in_one_launch(ctx, refs):
+    """n = 3200 keeps its f64 point state in LDS and n = 3201 in the arena; the choice is per pair inside a launch.  Both sides of
+    the seam and a small pair as ONE batch of stride 4096, each held as when it runs alone."""
+    cases, res, delta = refs
+    K, ns = rr.SEAM_BATCH
+    names = [f"K{K}_n{n}" for n in ns]
+    out = run(ctx, *stack([cases[k] for k in names]))
+    for b, (name, n) in enumerate(zip(names, ns)):
+        hold_to_reference(name, [o[b] for o in out], res[name], cases[name][1:], delta)
+        assert n - 2 <= out[4][b, 0] <= n, (name, out[4][b])      # what the seeds were chosen for: the pair is full to the seam
 
 
 def test_left_alone_rules_bit_for_bit(ctx, refs):

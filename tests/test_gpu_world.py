@@ -110,8 +110,7 @@ def test_hand_worked_cases_bit_exact(ctx, group):
     _hold_to_reference(view, lifted, scripts)
 
 
-def test_selection_at_8160_one_track_linked_neighbours_empty(ctx):
-    kp = 8160
+def _selection_one_track_linked_neighbours_empty(ctx, kp):
     rng = np.random.default_rng(5)
     m = np.stack([rng.permutation(kp), rng.permutation(kp)], 1)
     X = np.stack([rng.uniform(-2, 2, kp), rng.uniform(-2, 2, kp), rng.uniform(1, 9, kp)], 1)
@@ -123,6 +122,16 @@ def test_selection_at_8160_one_track_linked_neighbours_empty(ctx):
     view, lifted = _run_scripts(ctx, scripts, kp=kp, frames=3)
     assert view["links"][:, 1].tolist() == [0, kp, 0] and view["links"][:, 2].tolist() == [kp, kp, kp]
     _hold_to_reference(view, lifted, scripts, kp=kp)
+
+
+def test_selection_at_8160_one_track_linked_neighbours_empty(ctx):
+    _selection_one_track_linked_neighbours_empty(ctx, 8160)
+
+
+def test_selection_at_max_kp_one_track_linked_neighbours_empty(ctx):
+    """kp_stride = VSLAM_MAX_KP = 16384 (include/vslam_amd.h), the most the ABI takes: 128 KB of keys in the step kernel's LDS
+    beside its 1040 static bytes, every match slot used (full permutations), links == kp."""
+    _selection_one_track_linked_neighbours_empty(ctx, 16384)
 
 
 def test_device_sqrt_is_correctly_rounded(ctx):

@@ -25,7 +25,9 @@ def results():
 
 def test_inputs_participate_and_are_comparable(results):
     cases = {c[0]: c for c in rr.comparison_cases()}
-    assert len(results) == len(rr.COMPARISON_SHAPES) + len(rr.MIXED_BATCH[1])
+    seam = [f"K{rr.SEAM_BATCH[0]}_n{n}" for n in rr.SEAM_BATCH[1]]
+    assert len(results) == len(set(f"K{K}_n{n}" for K, n in rr.COMPARISON_SHAPES) | set(seam)) + len(rr.MIXED_BATCH[1])
+    assert all(name in results for name in seam) and sorted(rr.SEAM_BATCH[1])[-2:] == [3200, 3201]
     for name, out in results.items():
         info, n = out[4], int(cases[name][4][3])
         assert not info["left_alone"] and info["stats"][0] >= n - 2, name
