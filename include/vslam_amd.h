@@ -16,6 +16,32 @@
  *     VSLAM_OK == 0.  There is NO CPU fallback: without a HIP device every call fails.
  *   - Descriptors are 32 bytes per keypoint (cv::ORB default), points are (x, y) float pairs
  *     (cv::Point2f), index pairs are (queryIdx, trainIdx) int32.
+ *
+ * Alignment of device pointers
+ *   The caller's device memory may come from anywhere -- an allocation of its own, a slot of an arena, a slice of a larger
+ *   batch -- but the kernels read some arrays in wider units than their element type.  A KIND of array has one requirement
+ *   wherever it appears (the widest access any entry point makes through it, composite entry points included: what one entry
+ *   point writes the next one reads):
+ *     16 bytes   descriptors (d_desc*, d_obs_desc: uint4), the k-NN rows (d_knn: int4), homogeneous points (d_points4d,
+ *                d_map_points, d_points, the d_out of vslam_world_lift: float4), both buffers of vslam_debug_stream_copy;
+ *      8 bytes   keypoints and point pairs (d_xy*, d_queries, d_p1, d_p2: float2), index pairs (d_pairs, d_matches: int2),
+ *                f64 arrays (d_stats, d_error);
+ *      4 bytes   every other int32 / uint32 / float array: the alignment C gives its element type;
+ *     any address  image planes in and out (d_bgr, d_bgr_cur, d_bgr_out, d_gray, d_blurred, the d_out of vslam_gaussian7),
+ *                map colours (d_colors), the inlier mask (d_mask), the rBRIEF table (d_pattern), and what the copy calls move
+ *                (d_dst, d_src, d_ptr).  The kernels behind these read and write bytes, load unaligned, or are chosen by the
+ *                address: a plane on a 4- or 16-byte boundary whose width is a multiple of 4 or 16 gets the faster kernel,
+ *                and every choice gives the same bits.
+ *   A violated requirement is VSLAM_ERR_INVALID, and vslam_last_error names the argument.  The test is made on the host before
+ *   the entry point queues anything or touches the context's workspaces: a refused call leaves every output byte as it was,
+ *   and the context (or pipeline slot) is as usable as before.  Composite entry points (vslam_extract_features,
+ *   vslam_match_features, vslam_frontend_*, vslam_track_sequences, vslam_map_step, the vslam_pipeline_submit_* forms) test
+ *   all their arguments up front, members of `params` and `pose` included, so none of them fails half-way through a batch.
+ *   Where an entry point slices an array per frame, pair or track, the slices lie kp_stride x 32 / 16 / 8 bytes (or whole
+ *   elements) apart, so an aligned base aligns every slice: no stride can break it.  NULL passes every test (whether an
+ *   argument may be NULL is said at the entry point).  It is the address that is tested, not whether it starts an allocation.
+ *   tests/alignment_contract.py lists every pointer argument of this header with its requirement; tests/test_gpu_alignment.py
+ *   holds the entry points to it.
  */
 #ifndef VSLAM_AMD_H
 #define VSLAM_AMD_H
@@ -173,6 +199,7 @@ int vslam_prof_get(vslam_ctx *ctx, int i, char *name, int name_cap, double *tota
 
 /* profiling aid: a plain streaming copy of `bytes` (multiple of 16) with 4 or 16 bytes per lane, so
  * rocprofv3's FETCH_SIZE / WRITE_SIZE can be calibrated on a known byte count per access width */
+/* d_src, d_dst: 16-byte aligned (VSLAM_ERR_INVALID otherwise). */
 int vslam_debug_stream_copy(vslam_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, int bytes_per_lane);
 /* profiling aid: a kernel that keeps every SIMD's vector pipe busy for its whole duration (8 waves per SIMD of independent
  * v_fma_f32), so that rocprofv3's SQ_ACTIVE_INST_VALU / GRBM_GUI_ACTIVE ratio that means "vector pipe 100 % busy" is measured
@@ -185,7 +212,8 @@ int vslam_debug_valu_calib(vslam_ctx *ctx);
  * d_desc1/d_desc2: [batch][kp_stride][32] u8; d_n1/d_n2: [batch] int32.
  * d_pairs: [batch][kp_stride][2] int32 (queryIdx, trainIdx) in query order; d_m: [batch].
  * Optional d_knn (may be NULL): [batch][kp_stride][4] int32 = idx0, dist0, idx1, dist1.
- * Items with fewer than 2 train rows produce m = 0 (the reference reads m[1] regardless).    */
+ * Items with fewer than 2 train rows produce m = 0 (the reference reads m[1] regardless).
+ * Alignment: d_desc1, d_desc2, d_knn 16 bytes, d_pairs 8, the counts 4 (VSLAM_ERR_INVALID otherwise).    */
 int vslam_match_knn2_ratio(vslam_ctx *ctx, const uint8_t *d_desc1, const int32_t *d_n1,
                            const uint8_t *d_desc2, const int32_t *d_n2, int batch, int kp_stride,
                            int32_t *d_pairs, int32_t *d_m, int32_t *d_knn);
@@ -194,7 +222,8 @@ int vslam_match_knn2_ratio(vslam_ctx *ctx, const uint8_t *d_desc1, const int32_t
 /* Replaces RansacFilter::initialize_sets, src/RansacFilter.cpp:6-34, with the seed injected
  * (std::mt19937(seed) + libstdc++ uniform_int_distribution, draws without replacement).
  * d_seeds: [batch] u32; d_m: [batch] matches per item; d_sets: [batch][hyp][8] int32.
- * d_draw_scratch: [batch][hyp*8] u32 workspace.  Items with m < 8 get all-zero sets.          */
+ * d_draw_scratch: [batch][hyp*8] u32 workspace.  Items with m < 8 get all-zero sets.
+ * Alignment: 4 bytes for all four arrays.                                                     */
 int vslam_ransac_sets(vslam_ctx *ctx, const uint32_t *d_seeds, const int32_t *d_m, int batch,
                       int hyp, int32_t *d_sets, uint32_t *d_draw_scratch);
 
@@ -207,7 +236,9 @@ int vslam_ransac_sets(vslam_ctx *ctx, const uint32_t *d_seeds, const int32_t *d_
  *          d_matches [batch][kp_stride][2] int32 compacted inlier matches (n_out of them).
  * Workspaces: d_hypF [batch][hyp][9] f32, d_hyp_count [batch][hyp] int32, d_hyp_sum [batch][hyp] f32
  * (also the per-hypothesis outputs the parity tests read: every F always; every count and sum
- * with VSLAM_OPT_RANSAC_ALL_SUMS, otherwise those of the maximum-count hypotheses, see above). */
+ * with VSLAM_OPT_RANSAC_ALL_SUMS, otherwise those of the maximum-count hypotheses, see above).
+ * Alignment (here and for vslam_ransac_solve / _evaluate): d_xy1, d_xy2, d_pairs, d_matches 8 bytes, d_mask any address,
+ * every other array 4 (VSLAM_ERR_INVALID otherwise).                                           */
 int vslam_ransac_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2,
                              const int32_t *d_pairs, const int32_t *d_m, const int32_t *d_sets,
                              int batch, int kp_stride, int hyp, float threshold, float *d_F,
@@ -257,7 +288,8 @@ int vslam_ransac_evaluate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2
  * wave, then the wave sums in wave order -- the order depends on n alone, so a pair gives the same bits in every run, in any
  * batch, at any position.  One workgroup per item, any n up to kp_stride.
  * Stream-ordered on the context; allocates nothing and does not synchronise.  VSLAM_ERR_INVALID, before anything is queued,
- * for a null pointer (d_stats excepted), batch <= 0 or kp_stride <= 0.                                                   */
+ * for a null pointer (d_stats excepted), batch <= 0 or kp_stride <= 0, or an argument off its alignment: d_xy1, d_xy2,
+ * d_matches, d_stats 8 bytes, the others 4.                                                                               */
 int vslam_refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const int32_t *d_matches,
                             const int32_t *d_best, int batch, int kp_stride, const float *d_F_in,
                             float *d_F_out /* may alias d_F_in */, double *d_stats /* [batch][4], may be NULL */);
@@ -305,7 +337,8 @@ int vslam_refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_x
  * the four wave sums in wave order: a pair gives the same bits in every run, in any batch, at any position.  A point's f64
  * coordinates stay in f64 between iterations (in LDS, or in a workspace of the context's grow-only arena when n is above 3200).
  * Stream-ordered on the context; does not synchronise.  VSLAM_ERR_INVALID, before anything is queued, for a null pointer
- * (d_stats excepted), batch <= 0, kp_stride <= 0, max_iterations outside 1 .. 64, gate_sq not finite or <= 0.                */
+ * (d_stats excepted), batch <= 0, kp_stride <= 0, max_iterations outside 1 .. 64, gate_sq not finite or <= 0, or an argument
+ * off its alignment: d_points4d 16 bytes, d_xy1, d_xy2, d_matches, d_stats 8, the others 4.                                  */
 int vslam_refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const int32_t *d_matches, const int32_t *d_best,
                        int batch, int kp_stride, const float *h_K, float gate_sq, int max_iterations,
                        float *d_R /* [batch][9] in/out */, float *d_t /* [batch][3] in/out */, float *d_c2 /* [batch][12] out */,
@@ -319,7 +352,8 @@ int vslam_refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, c
  * LDS, 14 bytes per slot (two float coordinates, a 16-bit index, two 16-bit partition lists) and 4 more,
  * rounded up to 16, within 160 KB less 512 bytes: 14 * kp_stride + 4 <= 163328, that is
  * kp_stride <= VSLAM_KDTREE_MAX_KP = 11666, VSLAM_ERR_CAPACITY beyond — which is also the limit of
- * vslam_extract_features / vslam_frontend_* when they are asked for the trees (d_nodes != NULL).  */
+ * vslam_extract_features / vslam_frontend_* when they are asked for the trees (d_nodes != NULL).
+ * Alignment, for all four k-d entry points: d_xy and d_queries 8 bytes, every other array 4.      */
 #define VSLAM_KDTREE_MAX_KP 11666
 int vslam_kdtree_build(vslam_ctx *ctx, const float *d_xy, const int32_t *d_n, int batch,
                        int kp_stride, int32_t *d_nodes);
@@ -366,7 +400,9 @@ typedef struct vslam_extract_params {
  * d_bgr: [frames][height][row_stride] u8 (3 bytes per pixel).
  * Outputs per frame: d_xy [frames][kp_stride][2], d_desc [frames][kp_stride][32],
  * d_nodes [frames][kp_stride] (may be NULL), d_n [frames] kept keypoints, d_n_detected [frames]
- * (the pre-filter count that sizes map_point_ids, src/Frame.cpp:73).                          */
+ * (the pre-filter count that sizes map_point_ids, src/Frame.cpp:73).
+ * Alignment: d_bgr and params->d_pattern any address (any row_stride >= 3 * width as well); d_desc 16 bytes, d_xy 8,
+ * d_nodes, d_n, d_n_detected 4 -- all tested before the first stage is queued.               */
 int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int width, int height,
                            int row_stride, const vslam_extract_params *params, int kp_stride,
                            float *d_xy, uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n,
@@ -379,13 +415,18 @@ int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int
  * ORB::compute on the whole outlined image (:43).  Like the reference it builds no k-d tree and does
  * not touch map_point_ids.  Outputs per frame: d_xy [frames][kp_stride][2] (ORB::compute's order:
  * grouped by pyramid level), d_desc [frames][kp_stride][32], optional d_angle_octave
- * [frames][kp_stride][2] (degrees, level), d_n [frames].                                          */
+ * [frames][kp_stride][2] (degrees, level), d_n [frames].
+ * Alignment: d_bgr any address; d_pattern any address (a table off a 16-byte boundary is copied to an aligned one first);
+ * d_desc 16 bytes, d_xy 8, d_angle_octave and d_n 4.                                                   */
 int vslam_extract_features_grid(vslam_ctx *ctx, uint8_t *d_bgr, int frames, int width, int height,
                                 int row_stride, int nrows, int ncols, const int8_t *d_pattern,
                                 int kp_stride, float *d_xy, uint8_t *d_desc, float *d_angle_octave,
                                 int32_t *d_n);
 
-/* stage-level entry points (parity tests; each is one step of vslam_extract_features) */
+/* stage-level entry points (parity tests; each is one step of vslam_extract_features).  Alignment: every image plane
+ * (d_bgr, d_gray, d_out, d_blurred) and d_pattern at any address -- a plane whose base and width allow it gets the dword or
+ * 16-byte kernel, any other the byte kernel, with the same bits; d_desc 16 bytes, d_xy / d_xy_in / d_xy_out 8, d_eig and the
+ * counts 4 (d_eig on a 16-byte boundary gets float4 stores).                                           */
 int vslam_bgr2gray(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int width, int height,
                    int row_stride, uint8_t *d_gray);
 int vslam_min_eigen(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int width, int height,
@@ -404,7 +445,9 @@ int vslam_orb_describe(vslam_ctx *ctx, const uint8_t *d_blurred, int frames, int
 /* Replaces extract_Rt(fundamental, K, rotation, translation), src/helpers.cpp:3-35, for a batch of
  * fundamental matrices, plus the camera matrix c2 = K * [R | t] of src/vslam.cpp:83-85,125.
  * d_F [batch][9]; d_best [batch][4] as written by vslam_ransac_* (items with winner < 0 are skipped;
- * may be NULL); h_K: HOST 3x3 intrinsics (row-major).  d_R [batch][9], d_t [batch][3], d_c2 [batch][12]. */
+ * may be NULL); h_K: HOST 3x3 intrinsics (row-major).  d_R [batch][9], d_t [batch][3], d_c2 [batch][12].
+ * Alignment of the pose entry points (this one, vslam_triangulate, _triangulate_points, _reprojection_filter): d_points4d 16
+ * bytes, d_xy1, d_xy2, d_p1, d_p2, d_matches, d_error 8, every other device array 4.               */
 int vslam_extract_Rt(vslam_ctx *ctx, const float *d_F, const int32_t *d_best, int batch, const float *h_K,
                      float *d_R, float *d_t, float *d_c2);
 /* Replaces triangulate(p1, p2, c1, c2, points_4d), src/helpers.cpp:37-80, with c1 = [K | 0]
@@ -440,7 +483,8 @@ int vslam_reprojection_filter(vslam_ctx *ctx, const float *d_points4d, const flo
  * observations in CSR form: d_obs_offsets [batch][map_stride+1], d_obs_desc [batch][obs_stride][32];
  * d_map_point_ids [batch][kp_stride] in/out (-1 = free); d_claim [batch][map_stride] = keypoint or -1.
  * At most 16 acceptable hits per map point are kept; more sets a sticky flag that
- * vslam_ctx_synchronize reports as VSLAM_ERR_CAPACITY.                                            */
+ * vslam_ctx_synchronize reports as VSLAM_ERR_CAPACITY.
+ * Alignment: d_map_points, d_desc, d_obs_desc 16 bytes, d_xy 8, every other array 4.                */
 int vslam_associate_map_points(vslam_ctx *ctx, const float *d_map_points, const int32_t *d_n_map, int batch,
                                int map_stride, const float *d_c2, int img_w, int img_h,
                                const int32_t *d_nodes, const float *d_xy, const uint8_t *d_desc,
@@ -461,8 +505,8 @@ int vslam_associate_map_points(vslam_ctx *ctx, const float *d_map_points, const 
  * A map belongs to the context it was made on and is destroyed BEFORE it (vslam_map_destroy waits for the context's stream);
  * every call is stream-ordered on that context.  vslam_map_reset / _step / _view / _observations allocate nothing;
  * vslam_track_sequences takes its flattened seed row and the front-end's workspaces from the context's grow-only arena, like
- * vslam_frontend_sequence.  Descriptor arrays handed to a map call are 16-byte aligned, matches and points 8-byte aligned
- * (VSLAM_ERR_INVALID otherwise); match indices outside the frames' keypoint counts are ignored.  Frame ids count from 0 per track; `frames` = frames recorded so far (1 after create / reset: frame 0). */
+ * vslam_frontend_sequence.  Descriptor arrays handed to a map call are 16-byte aligned, matches and points 8-byte aligned,
+ * other int32 / float arrays 4-byte aligned (VSLAM_ERR_INVALID otherwise, before anything is queued); images (d_bgr, d_bgr_cur) at any address; match indices outside the frames' keypoint counts are ignored.  Frame ids count from 0 per track; `frames` = frames recorded so far (1 after create / reset: frame 0). */
 typedef struct vslam_map vslam_map;
 typedef struct vslam_map_arrays {
     int32_t tracks, max_frames, kp_stride, map_capacity, obs_capacity;
@@ -580,7 +624,7 @@ int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, 
  *
  * d_points [tracks][map_stride][4] f32, d_colors [tracks][map_stride][3] u8, d_sizes [tracks] int32; d_pose
  * [tracks][pose_stride][16] f32 (row-major 4 x 4; may be NULL when frames == 0 or VSLAM_RENDER_FRUSTA is not set),
- * 0 <= frames <= pose_stride; d_points is 16-byte and d_depth_out 4-byte aligned (VSLAM_ERR_INVALID otherwise).  d_bgr_out [tracks][height][row_stride] u8, row_stride >= 3 * width; bytes past 3 * width in a
+ * 0 <= frames <= pose_stride; d_points is 16-byte, d_sizes, d_pose and d_depth_out are 4-byte aligned (VSLAM_ERR_INVALID otherwise), d_colors and d_bgr_out may sit at any address.  d_bgr_out [tracks][height][row_stride] u8, row_stride >= 3 * width; bytes past 3 * width in a
  * row are not written.  d_depth_out (may be NULL) [tracks][height][width] f32: the winner's depth, +inf where nothing was drawn.
  * Both calls are stream-ordered on the context, take their key plane ([tracks][height][width] u64) from the context's grow-only
  * arena, do not synchronise (except when that plane has to grow: the arena then waits for the stream before it frees the old
@@ -680,7 +724,7 @@ int vslam_world_step(vslam_ctx *ctx, vslam_world *world, const int32_t *d_matche
                      const int32_t *d_n_cur);
 /* Lifts rows [d_lo[track], d_hi[track]) (clamped to 0 .. stride) of d_points [tracks][stride][4], points of pair
  * (frame - 1 -> frame), 1 <= frame < frames recorded, into d_out [tracks][stride][4]; rows outside the range keep their bits.
- * d_out may be d_points.  Both are 16-byte aligned.                                                                        */
+ * d_out may be d_points.  Both are 16-byte aligned, d_lo and d_hi 4-byte (VSLAM_ERR_INVALID otherwise).                      */
 int vslam_world_lift(vslam_ctx *ctx, vslam_world *world, int frame, const float *d_points, int stride, const int32_t *d_lo,
                      const int32_t *d_hi, float *d_out);
 int vslam_world_view(vslam_world *world, vslam_world_arrays *out);
@@ -701,7 +745,8 @@ int vslam_world_render(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int t
 /* ------------------------------------------------------------------ pipeline */
 /* match_features(frame1, frame2, rf, matches, F), src/Frame.cpp:82-105, for a batch of pairs
  * whose features are already on the device: match -> sets -> RANSAC -> inlier matches.
- * Workspaces are owned by the context and sized on first use.                                */
+ * Workspaces are owned by the context and sized on first use.
+ * Alignment: d_desc1, d_desc2 16 bytes, d_xy1, d_xy2, d_matches 8, every other array 4, tested up front. */
 int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_desc1,
                          const int32_t *d_n1, const float *d_xy2, const uint8_t *d_desc2,
                          const int32_t *d_n2, int batch, int kp_stride, const uint32_t *d_seeds,
@@ -712,7 +757,10 @@ int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_de
  * frames, frames [pairs, 2*pairs) the "current" ones; pair p = (frame p, frame pairs + p).
  * Extract all 2*pairs frames, match last->current, RANSAC.  This is what bench.py times.
  * d_xy / d_desc / d_nodes / d_n are the per-frame outputs of vslam_extract_features for all
- * 2*pairs frames; d_matches / d_best / d_F are per pair as in vslam_match_features.          */
+ * 2*pairs frames; d_matches / d_best / d_F are per pair as in vslam_match_features.
+ * Alignment as for vslam_extract_features and vslam_match_features, all of it tested before the first stage is queued
+ * (the same holds for vslam_frontend_pairs_pose, with pose->d_points4d 16 bytes and pose->d_error 8, and for
+ * vslam_frontend_sequence).                                                                   */
 int vslam_frontend_pairs(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, int width, int height,
                          int row_stride, const vslam_extract_params *params, int kp_stride,
                          const uint32_t *d_seeds, int hyp, float threshold,
@@ -742,7 +790,8 @@ int vslam_frontend_pairs_pose(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, i
 
 /* Fixed-size per-pair result records for the one exchange of the multi-GPU path: per pair
  * 13 + kp_stride int32 words = F (9 words, bit-preserving), d_best's 4 words, then one word per match slot,
- * query index | train index << 16 (keypoint indices are below VSLAM_MAX_KP).  d_records: [pairs][13 + kp_stride]. */
+ * query index | train index << 16 (keypoint indices are below VSLAM_MAX_KP).  d_records: [pairs][13 + kp_stride].
+ * Alignment: d_matches 8 bytes, the others 4.                                                                     */
 int vslam_pack_records(vslam_ctx *ctx, const float *d_F, const int32_t *d_best, const int32_t *d_matches,
                        int pairs, int kp_stride, int32_t *d_records);
 
@@ -771,7 +820,9 @@ int vslam_frontend_sequence(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, in
  *                            ticket only and does not reach the next batch of the same context);
  *   vslam_pipeline_submit_pairs / _sequence   acquire + vslam_frontend_pairs / _sequence (+ vslam_pack_records when
  *                            d_records is not NULL) + commit.  Output buffers are the caller's, one set per batch in flight.
- *                            An error of the wrapped call is returned at once, *ticket_out = -1, the slot stays usable;
+ *                            An error of the wrapped call is returned at once, *ticket_out = -1, the slot stays usable
+ *                            (an argument off its alignment is such an error: nothing of the batch is queued, nothing is
+ *                            filed under a ticket; d_records: 4 bytes);
  *   vslam_pipeline_wait      blocks until that batch is complete; returns its status (VSLAM_OK, VSLAM_ERR_CAPACITY, ...).
  *                            Statuses of failed batches nobody asked about are kept (the last 256);
  *   vslam_pipeline_poll      1 = complete, 0 = not yet (never blocks);
@@ -841,7 +892,7 @@ int vslam_multi_frontend_pairs(vslam_multi *m, const uint8_t *h_bgr_last, const 
  * frames are ALREADY on the devices (decoded there, produced by an earlier stage, uploaded ahead of time):
  * d_bgr[r] = slot r's slice on slot r's device in vslam_frontend_pairs' layout -- the slice's `last` frames, then its
  * `current` frames, (hi - lo) of each for [lo, hi) = vslam_shard_range(pairs, r, size) -- NULL allowed for an empty slice.
- * Everything else as above: records and counts come back to host memory in pair order.                                 */
+ * Everything else as above: records and counts come back to host memory in pair order.  The images: any address.           */
 int vslam_multi_frontend_pairs_resident(vslam_multi *m, const uint8_t *const *d_bgr, int pairs, int width, int height,
                                         int row_stride, const vslam_extract_params *params, const int8_t *h_pattern,
                                         int kp_stride, uint32_t base_seed, int hyp, float threshold, int32_t *h_records,
@@ -852,7 +903,8 @@ int vslam_multi_frontend_pairs_resident(vslam_multi *m, const uint8_t *const *d_
  *   vslam_comm_unique_id: rank 0 makes the 128-byte id and hands it to the other ranks by whatever channel the launcher
  *   has (a file, a socket, an environment variable, MPI); vslam_comm_create: collective over all ranks.
  *   vslam_gather_records: every rank contributes words_per_rank int32 (equal on all ranks: pad the last slice);
- *   d_all receives world x words_per_rank in rank order = pair order.  Asynchronous on the context's stream.          */
+ *   d_all receives world x words_per_rank in rank order = pair order.  Asynchronous on the context's stream.
+ *   d_records and d_all (here and in vslam_gather_records_v): 4-byte aligned.                                          */
 #define VSLAM_COMM_ID_BYTES 128
 typedef struct vslam_comm vslam_comm;
 int vslam_comm_unique_id(void *id_out);

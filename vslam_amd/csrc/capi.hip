@@ -185,6 +185,8 @@ int vslam_debug_valu_calib(vslam_ctx *ctx) {
 
 int vslam_debug_stream_copy(vslam_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, int bytes_per_lane) {
     if (!ctx || !d_src || !d_dst || (bytes_per_lane != 4 && bytes_per_lane != 16) || bytes % 16) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_src, 16);
+    VS_ALIGNED(ctx, d_dst, 16);
     if (bytes_per_lane == 4) {
         VsProfScope ps(ctx, "pmc_calib_copy4_kernel");
         pmc_calib_copy4_kernel<<<2048, 256, 0, ctx->stream>>>((const uint32_t *)d_src, (uint32_t *)d_dst, bytes / 4);
@@ -559,12 +561,19 @@ int vslam_match_knn2_ratio(vslam_ctx *ctx, const uint8_t *d_desc1, const int32_t
                            const uint8_t *d_desc2, const int32_t *d_n2, int batch, int kp_stride,
                            int32_t *d_pairs, int32_t *d_m, int32_t *d_knn) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // descriptor rows are read as uint4, pairs written as int2, the k-NN rows as int4 (match.hip)
+    VS_ALIGNED(ctx, d_desc1, 16);
+    VS_ALIGNED(ctx, d_desc2, 16);
+    VS_ALIGNED(ctx, d_knn, 16);
+    VS_ALIGNED(ctx, d_pairs, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n1, d_n2, d_m) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_match(ctx, d_desc1, d_n1, d_desc2, d_n2, batch, kp_stride, d_pairs, d_m, d_knn);
 }
 
 int vslam_ransac_sets(vslam_ctx *ctx, const uint32_t *d_seeds, const int32_t *d_m, int batch, int hyp,
                       int32_t *d_sets, uint32_t *d_draw_scratch) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, vs_ptr_bits(d_seeds, d_m, d_sets, d_draw_scratch) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_ransac_sets(ctx, d_seeds, d_m, batch, hyp, d_sets, d_draw_scratch);
 }
 
@@ -574,6 +583,12 @@ int vslam_ransac_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_
                              uint8_t *d_mask, int32_t *d_best, int32_t *d_matches, float *d_hypF,
                              int32_t *d_hyp_count, float *d_hyp_sum) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // points are read as float2, index pairs as int2 (ransac_*.hip); the mask is written byte by byte
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_pairs, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_m, d_sets, d_F, d_best, d_hypF, d_hyp_count, d_hyp_sum) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_ransac(ctx, d_xy1, d_xy2, d_pairs, d_m, d_sets, batch, kp_stride, hyp, threshold,
                             d_F, d_mask, d_best, d_matches, d_hypF, d_hyp_count, d_hyp_sum);
 }
@@ -582,6 +597,10 @@ int vslam_ransac_solve(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, c
                        const int32_t *d_m, const int32_t *d_sets, int batch, int kp_stride, int hyp,
                        float *d_hypF) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_pairs, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_m, d_sets, d_hypF) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_ransac_solve(ctx, d_xy1, d_xy2, d_pairs, d_m, d_sets, batch, kp_stride, hyp, d_hypF);
 }
 
@@ -590,6 +609,11 @@ int vslam_ransac_evaluate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2
                           int kp_stride, int hyp, float threshold, float *d_F, uint8_t *d_mask,
                           int32_t *d_best, int32_t *d_matches, int32_t *d_hyp_count, float *d_hyp_sum) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_pairs, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_m, d_hypF, d_F, d_best, d_hyp_count, d_hyp_sum) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_ransac_evaluate(ctx, d_xy1, d_xy2, d_pairs, d_m, d_hypF, batch, kp_stride, hyp, threshold,
                                      d_F, d_mask, d_best, d_matches, d_hyp_count, d_hyp_sum);
 }
@@ -597,6 +621,8 @@ int vslam_ransac_evaluate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2
 int vslam_kdtree_build(vslam_ctx *ctx, const float *d_xy, const int32_t *d_n, int batch, int kp_stride,
                        int32_t *d_nodes) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n, d_nodes) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_kdtree_build(ctx, d_xy, d_n, batch, kp_stride, d_nodes);
 }
 
@@ -604,6 +630,9 @@ int vslam_kdtree_radius(vslam_ctx *ctx, const int32_t *d_nodes, const float *d_x
                         int batch, int kp_stride, const float *d_queries, const int32_t *d_nq,
                         int q_stride, float radius, int32_t *d_hits, int32_t *d_counts, int hit_cap) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_ALIGNED(ctx, d_queries, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_nodes, d_n, d_nq, d_hits, d_counts) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_kdtree_radius(ctx, d_nodes, d_xy, d_n, batch, kp_stride, d_queries, d_nq, q_stride,
                                    radius, d_hits, d_counts, hit_cap);
 }
@@ -612,6 +641,9 @@ int vslam_kdtree_nearest(vslam_ctx *ctx, const int32_t *d_nodes, const float *d_
                          int batch, int kp_stride, const float *d_queries, const int32_t *d_nq,
                          int q_stride, float max_distance_sq, int32_t *d_best_idx) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_ALIGNED(ctx, d_queries, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_nodes, d_n, d_nq, d_best_idx) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_kdtree_nearest(ctx, d_nodes, d_xy, d_n, batch, kp_stride, d_queries, d_nq, q_stride,
                                     max_distance_sq, d_best_idx);
 }
@@ -619,6 +651,8 @@ int vslam_kdtree_nearest(vslam_ctx *ctx, const int32_t *d_nodes, const float *d_
 int vslam_kdtree_cell_table(vslam_ctx *ctx, const int32_t *d_nodes, const float *d_xy, const int32_t *d_n, int batch,
                             int kp_stride, int slots, uint32_t *d_table, int32_t *d_ok) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_nodes, d_n, d_table, d_ok) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_kdtree_cell_table(ctx, d_nodes, d_xy, d_n, batch, kp_stride, slots, d_table, d_ok);
 }
 
@@ -636,6 +670,8 @@ int vslam_bgr2gray(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int width, 
 int vslam_min_eigen(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int width, int height,
                     float *d_eig) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // d_gray: any address (the dword kernel is chosen by its alignment); d_eig: float4 stores only on a 16-byte boundary
+    VS_REQUIRE(ctx, vs_ptr_bits(d_eig) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_min_eigen(ctx, d_gray, frames, width, height, width, d_eig, nullptr);
 }
 
@@ -643,6 +679,8 @@ int vslam_good_features(vslam_ctx *ctx, const uint8_t *d_gray, int frames, int w
                         int max_corners, double quality, double min_distance, int kp_stride,
                         float *d_xy, int32_t *d_n) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n) % 4 == 0, VSLAM_ERR_INVALID);
     const int pitch = vs_padded_pitch(width);
     if (d_gray && pitch != width && frames > 0 && height > 0) {   // see vslam_extract_features: the caller's rows, copied into padded ones
         uint8_t *padded = nullptr;
@@ -675,6 +713,11 @@ int vslam_orb_describe(vslam_ctx *ctx, const uint8_t *d_blurred, int frames, int
                        float sin_a, const int8_t *d_pattern, float *d_xy_out, uint8_t *d_desc,
                        int32_t *d_n_out) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // the blurred plane and the pattern: any address (vs_launch_orb_describe picks the kernel; the pattern is read by bytes)
+    VS_ALIGNED(ctx, d_xy_in, 8);
+    VS_ALIGNED(ctx, d_xy_out, 8);
+    VS_ALIGNED(ctx, d_desc, 16);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n_in, d_n_out) % 4 == 0, VSLAM_ERR_INVALID);
     if (!d_pattern)
         if (int rc = vs_default_pattern(ctx, &d_pattern)) return rc;
     return vs_launch_orb_describe(ctx, d_blurred, frames, width, height, width, d_xy_in, d_n_in, kp_stride,
@@ -701,6 +744,8 @@ int vslam_extract_features(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, int
                            float *d_xy, uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n,
                            int32_t *d_n_detected) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    if (int arc = vs_frontend_aligned(ctx, nullptr, d_xy, d_desc, d_nodes, d_n, nullptr, nullptr, nullptr)) return arc;
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n_detected) % 4 == 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_bgr && params && d_xy && d_desc && d_n, VSLAM_ERR_INVALID);
     vslam_extract_params with_table;
     if (!params->d_pattern) {   // the default: ORB's learned table
@@ -764,6 +809,10 @@ int vslam_extract_features_grid(vslam_ctx *ctx, uint8_t *d_bgr, int frames, int 
                                 int nrows, int ncols, const int8_t *d_pattern, int kp_stride, float *d_xy,
                                 uint8_t *d_desc, float *d_angle_octave, int32_t *d_n) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // d_bgr: any address (grid_outline_gray_kernel); d_pattern: any address (copied to an aligned table when off a 16-byte boundary)
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_ALIGNED(ctx, d_desc, 16);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_angle_octave, d_n) % 4 == 0, VSLAM_ERR_INVALID);
     if (!d_pattern)
         if (int rc = vs_default_pattern(ctx, &d_pattern)) return rc;
     return vs_launch_extract_grid(ctx, d_bgr, frames, width, height, row_stride, nrows, ncols, d_pattern, kp_stride,
@@ -774,6 +823,10 @@ int vslam_extract_features_grid(vslam_ctx *ctx, uint8_t *d_bgr, int frames, int 
 int vslam_triangulate_points(vslam_ctx *ctx, const float *d_p1, const float *d_p2, int n, const float *h_c1,
                              const float *h_c2, float *d_points4d) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // point pairs as float2, results as float4 (pose.hip)
+    VS_ALIGNED(ctx, d_p1, 8);
+    VS_ALIGNED(ctx, d_p2, 8);
+    VS_ALIGNED(ctx, d_points4d, 16);
     return vs_launch_triangulate_points(ctx, d_p1, d_p2, n, h_c1, h_c2, d_points4d);
 }
 
@@ -781,6 +834,7 @@ int vslam_triangulate_points(vslam_ctx *ctx, const float *d_p1, const float *d_p
 int vslam_extract_Rt(vslam_ctx *ctx, const float *d_F, const int32_t *d_best, int batch, const float *h_K, float *d_R,
                      float *d_t, float *d_c2) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, vs_ptr_bits(d_F, d_best, d_R, d_t, d_c2) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_extract_Rt(ctx, d_F, d_best, batch, h_K, d_R, d_t, d_c2);
 }
 
@@ -789,6 +843,11 @@ int vslam_triangulate(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, co
                       const int32_t *d_best, int batch, int kp_stride, const float *h_K, const float *d_c2,
                       float *d_points4d) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_ALIGNED(ctx, d_points4d, 16);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_c2) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_triangulate(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, h_K, d_c2, d_points4d);
 }
 
@@ -798,6 +857,12 @@ int vslam_reprojection_filter(vslam_ctx *ctx, const float *d_points4d, const flo
                               const float *d_c2, const int32_t *d_map_point_ids, float threshold_sq, int32_t *d_inlier_idx,
                               int32_t *d_n_inliers, double *d_error) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_points4d, 16);
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_c2, d_map_point_ids, d_inlier_idx, d_n_inliers) % 4 == 0, VSLAM_ERR_INVALID);
+    VS_ALIGNED(ctx, d_error, 8);
     return vs_launch_reproj_filter(ctx, d_points4d, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, h_K, d_c2,
                                    d_map_point_ids, threshold_sq, d_inlier_idx, d_n_inliers, d_error);
 }
@@ -809,6 +874,12 @@ int vslam_associate_map_points(vslam_ctx *ctx, const float *d_map_points, const 
                                const uint8_t *d_obs_desc, int obs_stride, float radius, uint32_t dist_threshold,
                                int32_t *d_map_point_ids, int32_t *d_claim) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // map points as float4, descriptors as uint4, keypoints as float2 (assoc.hip)
+    VS_ALIGNED(ctx, d_map_points, 16);
+    VS_ALIGNED(ctx, d_desc, 16);
+    VS_ALIGNED(ctx, d_obs_desc, 16);
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n_map, d_c2, d_nodes, d_n, d_obs_offsets, d_map_point_ids, d_claim) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_associate(ctx, d_map_points, d_n_map, batch, map_stride, d_c2, img_w, img_h, d_nodes, d_xy, d_desc, d_n,
                                kp_stride, d_obs_offsets, d_obs_desc, obs_stride, radius, dist_threshold, d_map_point_ids,
                                d_claim);
@@ -859,6 +930,12 @@ int vslam_match_features(vslam_ctx *ctx, const float *d_xy1, const uint8_t *d_de
                          int hyp, float threshold, int32_t *d_matches, int32_t *d_best, float *d_F,
                          int32_t *d_prelim_m) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_desc1, 16);
+    VS_ALIGNED(ctx, d_desc2, 16);
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n1, d_n2, d_seeds, d_best, d_F, d_prelim_m) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_match_features(ctx, d_xy1, d_desc1, d_n1, d_xy2, d_desc2, d_n2, batch, kp_stride, d_seeds, hyp, threshold, d_matches,
                              d_best, d_F, d_prelim_m, false);
 }
@@ -890,6 +967,7 @@ int vslam_frontend_pairs(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, int wi
                          uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches,
                          int32_t *d_best, float *d_F) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    if (int arc = vs_frontend_aligned(ctx, d_seeds, d_xy, d_desc, d_nodes, d_n, d_matches, d_best, d_F)) return arc;
     VS_REQUIRE(ctx, pairs > 0, VSLAM_ERR_INVALID);
     // The k-d trees are an output of the path but not an input of match/RANSAC: build them on the
     // auxiliary stream beside the matching stages (fork after extraction, join at the end).  With
@@ -924,6 +1002,12 @@ int vslam_frontend_pairs_pose(vslam_ctx *ctx, const uint8_t *d_bgr, int pairs, i
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, h_K && pose, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, pose->d_R && pose->d_t && pose->d_c2 && pose->d_points4d && pose->d_inlier_idx && pose->d_n_inliers && pose->d_error,
+               VSLAM_ERR_INVALID);
+    // everything the chain is handed, before its first stage is queued
+    if (int arc = vs_frontend_aligned(ctx, d_seeds, d_xy, d_desc, d_nodes, d_n, d_matches, d_best, d_F)) return arc;
+    VS_ALIGNED(ctx, pose->d_points4d, 16);
+    VS_ALIGNED(ctx, pose->d_error, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_map_point_ids, pose->d_R, pose->d_t, pose->d_c2, pose->d_inlier_idx, pose->d_n_inliers) % 4 == 0,
                VSLAM_ERR_INVALID);
     int rc = vslam_frontend_pairs(ctx, d_bgr, pairs, width, height, row_stride, params, kp_stride, d_seeds, hyp, threshold, d_xy,
                                   d_desc, d_nodes, d_n, d_matches, d_best, d_F);
@@ -969,6 +1053,8 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const float *__restri
 int vslam_pack_records(vslam_ctx *ctx, const float *d_F, const int32_t *d_best, const int32_t *d_matches,
                        int pairs, int kp_stride, int32_t *d_records) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_F, d_best, d_records) % 4 == 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_F && d_best && d_matches && d_records, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, pairs > 0 && kp_stride > 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, kp_stride <= VSLAM_MAX_KP, VSLAM_ERR_CAPACITY);
@@ -985,6 +1071,7 @@ int vslam_frontend_sequence(vslam_ctx *ctx, const uint8_t *d_bgr, int frames, in
                             uint8_t *d_desc, int32_t *d_nodes, int32_t *d_n, int32_t *d_matches,
                             int32_t *d_best, float *d_F) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    if (int arc = vs_frontend_aligned(ctx, d_seeds, d_xy, d_desc, d_nodes, d_n, d_matches, d_best, d_F)) return arc;
     VS_REQUIRE(ctx, frames >= 2, VSLAM_ERR_INVALID);
     const bool overlap = d_nodes && !ctx->prof && ctx->tree_fork != 5;   // k-d trees beside the matching stages, as in vslam_frontend_pairs
     bool raw_ready;

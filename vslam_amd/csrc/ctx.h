@@ -99,6 +99,29 @@ struct vslam_ctx {
         }                                                                                   \
     } while (0)
 
+// The pointer-alignment contract of include/vslam_amd.h ("Alignment of device pointers"): a caller's device pointer on a
+// multiple of `bytes`, checked on the host in front of the entry point's first launch and before it touches the arena.  The
+// message names the argument.  A null pointer passes: whether an argument may be null is the entry point's own question.
+#define VS_ALIGNED(ctx, ptr, bytes) VS_REQUIRE(ctx, reinterpret_cast<uintptr_t>(ptr) % (bytes) == 0, VSLAM_ERR_INVALID)
+// the int32 / float / f64 arrays, whose requirement is their element's own: VS_REQUIRE(ctx, vs_ptr_bits(a, b, c) % 4 == 0, ...)
+template <typename... P>
+static inline uintptr_t vs_ptr_bits(const P *...p) {
+    return (uintptr_t(0) | ... | reinterpret_cast<uintptr_t>(p));
+}
+// what every batched front-end call is handed (vslam_extract_features, vslam_frontend_*, vslam_track_sequences, the pipeline's
+// submit forms): all of it checked before the first stage is queued, so that no call fails half-way through a batch.  Every
+// per-frame and per-pair slice starts a multiple of kp_stride x 8 / 32 bytes (or whole int32s) behind its base, so the base
+// decides for all of them.  The image (d_bgr) and the pattern are taken at any address.
+static inline int vs_frontend_aligned(vslam_ctx *ctx, const uint32_t *d_seeds, const float *d_xy, const uint8_t *d_desc,
+                                      const int32_t *d_nodes, const int32_t *d_n, const int32_t *d_matches,
+                                      const int32_t *d_best, const float *d_F) {
+    VS_ALIGNED(ctx, d_desc, 16);
+    VS_ALIGNED(ctx, d_xy, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_seeds, d_nodes, d_n, d_best, d_F) % 4 == 0, VSLAM_ERR_INVALID);
+    return VSLAM_OK;
+}
+
 // sticky device-side error word (bit 0: a fixed-size candidate list overflowed); vslam_ctx_synchronize
 // reads and clears it and reports VSLAM_ERR_CAPACITY
 int vs_device_errflag(vslam_ctx *ctx, int32_t **out);

@@ -645,6 +645,7 @@ int vslam_map_view(vslam_map *map, vslam_map_arrays *out) {
 int vslam_map_observations(vslam_ctx *ctx, vslam_map *map, int32_t *d_offsets, int32_t *d_frame_ids, int32_t *d_point_ids) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, map && map->ctx == ctx && d_offsets && d_frame_ids && d_point_ids, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_offsets, d_frame_ids, d_point_ids) % 4 == 0, VSLAM_ERR_INVALID);
     const MapDev d = dev_of(map);
     map_offsets_kernel<<<map->tracks, kMT, 0, ctx->stream>>>(map->obs_cnt, map->sizes, map->map_capacity, map->map_capacity, d_offsets);
     map_csr_kernel<<<dim3(vs_div_up(2 * map->obs_capacity, kMT), map->tracks), kMT, 0, ctx->stream>>>(d, nullptr, map->sizes, d_offsets,
@@ -663,9 +664,13 @@ int vslam_map_step(vslam_ctx *ctx, vslam_map *map, const float *d_xy_last, const
     VS_REQUIRE(ctx, d_xy_last && d_desc_last && d_n_last && d_xy_cur && d_desc_cur && d_nodes_cur && d_n_cur, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_matches && d_best && d_F && d_bgr_cur && h_K, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, width > 0 && height > 0 && row_stride >= 3 * width, VSLAM_ERR_INVALID);
-    // descriptor rows move as uint4 pairs, matches and points as 8-byte pairs
-    VS_REQUIRE(ctx, (uintptr_t)d_desc_last % 16 == 0 && (uintptr_t)d_desc_cur % 16 == 0, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, (uintptr_t)d_matches % 8 == 0 && (uintptr_t)d_xy_last % 8 == 0 && (uintptr_t)d_xy_cur % 8 == 0, VSLAM_ERR_INVALID);
+    // descriptor rows move as uint4 pairs, matches and points as 8-byte pairs; the image is sampled by bytes
+    VS_ALIGNED(ctx, d_desc_last, 16);
+    VS_ALIGNED(ctx, d_desc_cur, 16);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_ALIGNED(ctx, d_xy_last, 8);
+    VS_ALIGNED(ctx, d_xy_cur, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_n_last, d_nodes_cur, d_n_cur, d_best, d_F) % 4 == 0, VSLAM_ERR_INVALID);
     return map_step(ctx, map, d_xy_last, d_desc_last, d_n_last, d_xy_cur, d_desc_cur, d_nodes_cur, d_n_cur, d_matches, d_best, d_F,
                     d_bgr_cur, (size_t)height * row_stride, width, height, row_stride, h_K, radius, dist_threshold,
                     reproj_threshold_sq);
@@ -680,7 +685,7 @@ int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, 
     VS_REQUIRE(ctx, d_bgr && params && d_seeds && h_K && d_xy && d_desc && d_nodes && d_n && d_matches && d_best && d_F,
                VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, frames >= 2 && width > 0 && height > 0 && row_stride >= 3 * width, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, (uintptr_t)d_desc % 16 == 0 && (uintptr_t)d_matches % 8 == 0 && (uintptr_t)d_xy % 8 == 0, VSLAM_ERR_INVALID);
+    if (int arc = vs_frontend_aligned(ctx, d_seeds, d_xy, d_desc, d_nodes, d_n, d_matches, d_best, d_F)) return arc;
     const int T = map->tracks, K = map->kp_stride;
     int rc;
     if ((rc = vslam_map_reset(ctx, map))) return rc;

@@ -465,6 +465,7 @@ int vslam_comm_info(vslam_comm *c, int *world_out, int *rank_out) {
 int vslam_gather_records(vslam_ctx *ctx, vslam_comm *comm, const int32_t *d_records, size_t words_per_rank, int32_t *d_all) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, comm && comm->comm && d_records && d_all && words_per_rank > 0, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_records, d_all) % 4 == 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, comm->device == ctx->device, VSLAM_ERR_INVALID);
     VS_HIP(ctx, hipSetDevice(ctx->device));
     VS_HIP(ctx, comm_order_before(comm, ctx->stream));
@@ -485,6 +486,7 @@ int vslam_gather_records_v(vslam_ctx *ctx, vslam_comm *comm, const int32_t *d_re
                            int32_t *d_all) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, comm && comm->comm && h_words && root < comm->world, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_records, d_all) % 4 == 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, comm->device == ctx->device, VSLAM_ERR_INVALID);
     const int world = comm->world, me = comm->rank;
     const bool receiver = root < 0 || root == me;

@@ -269,6 +269,10 @@ int vslam_pipeline_submit_pairs(vslam_pipeline *p, const uint8_t *d_bgr, int pai
     if (!p || !ticket_out) return VSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     *ticket_out = -1;
+    if (reinterpret_cast<uintptr_t>(d_records) % 4 != 0) {   // vslam_pack_records runs behind the front-end: refused before a ticket is taken
+        p->err = "requirement failed: d_records on a 4-byte boundary";
+        return VSLAM_ERR_INVALID;
+    }
     vslam_ctx *c = nullptr;
     int64_t t = -1;
     int rc = acquire_locked(p, &c, &t);
@@ -302,6 +306,10 @@ int vslam_pipeline_submit_pairs_pose(vslam_pipeline *p, const uint8_t *d_bgr, in
     if (!p || !ticket_out || !h_K || !pose) return VSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     *ticket_out = -1;
+    if (reinterpret_cast<uintptr_t>(d_records) % 4 != 0) {   // vslam_pack_records runs behind the front-end: refused before a ticket is taken
+        p->err = "requirement failed: d_records on a 4-byte boundary";
+        return VSLAM_ERR_INVALID;
+    }
     vslam_ctx *c = nullptr;
     int64_t t = -1;
     int rc = acquire_locked(p, &c, &t);
@@ -335,6 +343,10 @@ int vslam_pipeline_submit_sequence(vslam_pipeline *p, const uint8_t *d_bgr, int 
     if (!p || !ticket_out) return VSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     *ticket_out = -1;
+    if (reinterpret_cast<uintptr_t>(d_records) % 4 != 0) {   // vslam_pack_records runs behind the front-end: refused before a ticket is taken
+        p->err = "requirement failed: d_records on a 4-byte boundary";
+        return VSLAM_ERR_INVALID;
+    }
     vslam_ctx *c = nullptr;
     int64_t t = -1;
     int rc = acquire_locked(p, &c, &t);

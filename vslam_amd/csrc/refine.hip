@@ -315,6 +315,12 @@ extern "C" int vslam_refine_pairs(vslam_ctx *ctx, const float *d_xy1, const floa
                                   const int32_t *d_best, int batch, int kp_stride, const float *h_K, float gate_sq, int max_iterations,
                                   float *d_R, float *d_t, float *d_c2, float *d_points4d, double *d_stats) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_ALIGNED(ctx, d_points4d, 16);
+    VS_ALIGNED(ctx, d_stats, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_R, d_t, d_c2) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_refine_pairs(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, h_K, gate_sq, max_iterations, d_R, d_t, d_c2,
                                   d_points4d, d_stats);
 }

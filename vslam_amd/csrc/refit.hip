@@ -307,5 +307,10 @@ extern "C" int vslam_refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const
                                        const int32_t *d_best, int batch, int kp_stride, const float *d_F_in, float *d_F_out,
                                        double *d_stats) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    VS_ALIGNED(ctx, d_xy1, 8);
+    VS_ALIGNED(ctx, d_xy2, 8);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_ALIGNED(ctx, d_stats, 8);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_F_in, d_F_out) % 4 == 0, VSLAM_ERR_INVALID);
     return vs_launch_refit(ctx, d_xy1, d_xy2, d_matches, d_best, batch, kp_stride, d_F_in, d_F_out, d_stats);
 }

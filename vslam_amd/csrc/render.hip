@@ -225,7 +225,6 @@ int render_launch(vslam_ctx *ctx, const float *points, const uint8_t *colors, co
     VS_REQUIRE(ctx, std::isfinite(hv->z_near) && hv->z_near > 0.f && hv->z_far >= hv->z_near, VSLAM_ERR_INVALID);
     const bool frusta = (hv->flags & VSLAM_RENDER_FRUSTA) && frames > 0;
     VS_REQUIRE(ctx, !frusta || pose, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, (uintptr_t)points % 16 == 0 && (uintptr_t)depth % 4 == 0, VSLAM_ERR_INVALID);   // float4 rows
     VS_REQUIRE(ctx, W <= 16384 && H <= 16384 && tracks <= 65535 && frames <= (1 << 20), VSLAM_ERR_CAPACITY);
     RenderView v;
     for (int i = 0; i < 12; i++) v.mv[i] = (double)hv->mv[i];
@@ -322,6 +321,9 @@ int vslam_render_points(vslam_ctx *ctx, const float *d_points, const uint8_t *d_
                         int map_stride, const float *d_pose, int frames, int pose_stride, const vslam_view *h_view, int width,
                         int height, int row_stride, uint8_t *d_bgr_out, float *d_depth_out) {
     if (!ctx) return VSLAM_ERR_INVALID;
+    // float4 rows; the colours and the image are read and written by bytes (a lane's 12 bytes as dwords only where they are aligned)
+    VS_ALIGNED(ctx, d_points, 16);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_sizes, d_pose, d_depth_out) % 4 == 0, VSLAM_ERR_INVALID);
     return render_launch(ctx, d_points, d_colors, d_sizes, tracks, map_stride, d_pose, frames, pose_stride, h_view, width, height,
                          row_stride, d_bgr_out, d_depth_out);
 }
@@ -330,6 +332,7 @@ int vslam_map_render(vslam_ctx *ctx, vslam_map *map, int track_lo, int track_cou
                      int height, int row_stride, uint8_t *d_bgr_out, float *d_depth_out) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, map, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_depth_out) % 4 == 0, VSLAM_ERR_INVALID);
     vslam_map_arrays a;
     const int rc = vslam_map_view(map, &a);
     if (rc != VSLAM_OK) return rc;

@@ -416,10 +416,7 @@ __device__ __forceinline__ void tier_step(TierState &st, TierArgs &a, int t, int
             const uint8_t *rowp = a.src + (size_t)reflect101(a.ys - 3 + tn, a.h) * a.bstride;
             uint32_t oc = a.voff_c;
             asm volatile("" : "+v"(oc) : "v"(u0), "v"(u1), "v"(u2), "v"(u3));
-            const uint32_t *vp = reinterpret_cast<const uint32_t *>(rowp + oc);
-            st.raw[P][0] = vp[0];
-            st.raw[P][1] = vp[1];
-            st.raw[P][2] = vp[2];
+            __builtin_memcpy(st.raw[P], rowp + oc, 12);   // twelve bytes wherever they start: any base, any row stride
         }
         g[2] = cvt_ubyte<2>(u0); g[3] = cvt_ubyte<2>(u1); g[4] = cvt_ubyte<2>(u2); g[5] = cvt_ubyte<2>(u3);
         const uint32_t p01 = __builtin_amdgcn_perm(u1, u0, 0x0c0c0602u);
@@ -708,8 +705,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         st.trm[k] = 0.f;
         if constexpr (BGR) {
             const uint8_t *rowp = a.src + (size_t)reflect101(a.ys - 3 + k, h) * bstride;
-            const uint32_t *vp = reinterpret_cast<const uint32_t *>(rowp + a.voff_c);
-            st.raw[k][0] = vp[0]; st.raw[k][1] = vp[1]; st.raw[k][2] = vp[2];
+            __builtin_memcpy(st.raw[k], rowp + a.voff_c, 12);   // (as bgr2gray_padded_kernel loads them: no aligned dword is promised)
         } else {
             const uint8_t *rowp = a.src + (size_t)reflect101(a.ys - 3 + k, h) * bstride;
             st.raw[k][0] = *reinterpret_cast<const uint32_t *>(rowp + a.voff_l);

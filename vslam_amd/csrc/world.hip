@@ -353,7 +353,9 @@ int vslam_world_step(vslam_ctx *ctx, vslam_world *world, const int32_t *d_matche
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, world && world->ctx == ctx, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_matches && d_best && d_points4d && d_R && d_t && d_n_last && d_n_cur, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, (uintptr_t)d_matches % 8 == 0 && (uintptr_t)d_points4d % 16 == 0, VSLAM_ERR_INVALID);   // int2 / float4 rows
+    VS_ALIGNED(ctx, d_matches, 8);      // int2 rows
+    VS_ALIGNED(ctx, d_points4d, 16);    // float4 rows
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_R, d_t, d_n_last, d_n_cur) % 4 == 0, VSLAM_ERR_INVALID);
     return world_step(ctx, world, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur);
 }
 
@@ -363,7 +365,9 @@ int vslam_world_lift(vslam_ctx *ctx, vslam_world *world, int frame, const float 
     VS_REQUIRE(ctx, world && world->ctx == ctx, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_points && d_lo && d_hi && d_out && stride > 0, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, frame >= 1 && frame < world->frames, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, (uintptr_t)d_points % 16 == 0 && (uintptr_t)d_out % 16 == 0, VSLAM_ERR_INVALID);
+    VS_ALIGNED(ctx, d_points, 16);
+    VS_ALIGNED(ctx, d_out, 16);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_lo, d_hi) % 4 == 0, VSLAM_ERR_INVALID);
     return world_lift(ctx, world, frame, d_points, stride, d_lo, d_hi, d_out);
 }
 
@@ -380,6 +384,7 @@ int vslam_world_render(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int t
                        int width, int height, int row_stride, uint8_t *d_bgr_out, float *d_depth_out) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, world && world->ctx == ctx && map, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, vs_ptr_bits(d_depth_out) % 4 == 0, VSLAM_ERR_INVALID);
     vslam_map_arrays a;
     const int rc = vslam_map_view(map, &a);
     if (rc != VSLAM_OK) return rc;
