@@ -18,7 +18,8 @@ using namespace vs_ransac;
 //   ransac_rank_kernel    exact counts of 8 pilot hypotheses (a first lower bound on the maximum) and, from their
 //                         inlier masks, the matches ordered by how many pilots miss them (most-missed first), laid
 //                         out as four coordinate arrays;
-//   ransac_screen_kernel  every hypothesis on the 128 most-missed matches: how many of those it can have as inliers;
+//   ransac_screen_kernel  every hypothesis on the 128 most-missed matches (the head): how many of those it can have as
+//                         inliers, how many it certainly has, and the sum of its cheap values there;
 //   ransac_cand_kernel    exact full counts of the (up to 8) hypotheses that do best there -> the bound is now the
 //                         pair's maximum count on almost every pair;
 //   ransac_count_kernel   exact inlier count of every hypothesis that can reach the maximum (those that do are always
@@ -63,12 +64,36 @@ using namespace vs_ransac;
 // evaluations).  (2) The order: the matches every decent hypothesis misses are looked at first, so the allowance of
 // outliers is used up at once and the first real difference decides.  Counts do not depend on the order of the
 // matches, the cheap sums only within their certified bound, and ransac_tiesum_kernel sums in list order.
+// The test comes after every 256-match sub-block (a check every 128 cost more than it saved: the kernel is bound by what a
+// sub-block costs, not by evaluations), and the walk begins BEHIND the head: the screen has evaluated the head for every
+// hypothesis already, so a survivor starts with seen = n0 = min(m, 128) and pot = pot0, and its first sub-block is ranked
+// matches [n0, n0 + 256).  With D = m - bound + 1 certain outliers needed, the first exit comes at 384 matches seen instead
+// of 512 whenever D mod 256 lies in (0, 128] -- one sub-block less for most hypotheses of a pair with 40-45 % outliers.
+//
+// Full counts stay the reference's.  The screen hands on, beside pot0, the head's certain inliers (g < lo) and the sum of
+// the head's cheap values, or "not certified" after a zero / denormal / NaN dd.  A survivor with pot0 == certain (every
+// head evaluation decided outside the band, with a certified band: !B.ok gives lo = -1, certain = 0) takes that count; any
+// other survivor that completes its walk evaluates the head block itself as one more sub-block -- band, queue and exact
+// sequence as everywhere -- and uses its own sum of the head's cheap values instead of the screen's.
+//
+// The cheap sum S~ and its error.  Per evaluation |g - e| <= 12 u max(g, e) + beta (2 sqrt(g) + beta); summed with
+// Cauchy-Schwarz: |sum g - sum e| <= 2.02 beta sqrt(M S) + M beta^2 + 12 u (1 + ..) S over M evaluations.  S~ is formed in
+// float from non-negative terms, so every addition on the way costs a relative u: S~ = (sum g)(1 + d), |d| <= A u for A
+// additions on the longest path.  The tree is now: per lane two accumulators, two additions each per sub-block (the head block
+// included where it is evaluated here); one addition across the two; six across the lanes (wave_sum_to_lane63); one that adds
+// the screen's head sum, itself seven additions deep (ransac_screen_kernel) -- A <= 2 nsub + 9, one or two more than the walk
+// from zero had for the same m (2 nsub' + 7 with nsub' = ceil(m / 256) >= nsub).  The relative term 2^-18 = 64 u of the error
+// bound covers 12 u (1 + ..) + A u up to A = 51, i.e. 21 sub-blocks; for longer walks (more than about 5500 matches) the term
+// is (13 + A) u instead (cnt_sum_rel): stated here because the constant alone did not cover them before either.  The sum
+// rule uses the same expression over the `seen` evaluations so far, with the screen's head sum as their first part, and
+// does not fire for a hypothesis whose head is not certified.
 //
 // Mapping of the count kernel: a workgroup = 128 hypotheses of a pair; those the screen has not already ruled out are
-// handed to its 8 waves one at a time; a wave walks the ranked matches 256 at a time (4 per lane, coordinates staged in
-// LDS as four arrays so that a lane's two neighbouring matches are the halves of a packed operand); the hypothesis'
-// record (F twice, lo, hi) is a broadcast read from LDS; v_cmp writes lane masks to SGPRs, counting is s_bcnt1 on the
-// scalar unit (north_star: ballot / popcount).
+// handed to its 8 waves one at a time; a wave walks the ranked matches behind the head 256 at a time (4 per lane,
+// coordinates staged in LDS as four arrays so that a lane's two neighbouring matches are the halves of a packed operand; the
+// arrays are padded so that whole sub-blocks exist from ranked match 0 and from ranked match 128: cnt_pad); the hypothesis'
+// record (F twice, lo, hi) is a broadcast read from LDS, and so is what the screen found for it; v_cmp writes lane masks
+// to SGPRs, counting is s_bcnt1 on the scalar unit (north_star: ballot / popcount).
 constexpr int kCntHyps = 128;
 constexpr int kCntWaves = 8;
 constexpr int kCntQueue = 320;          // words per wave: the 256 evaluations of one sub-block + 63 carried over
@@ -92,7 +117,18 @@ constexpr int kCntRec = 12;
 typedef __attribute__((address_space(3))) volatile uint32_t cnt_queue_t;
 static_assert(VSLAM_MAX_KP <= 65536, "queue words keep the match index in 16 bits");
 
+// Slots per ranked coordinate array for n matches: whole 256-match sub-blocks from ranked match 0.  The count kernel's walk
+// starts at ranked match kScreenMatches, so its last sub-block can reach up to 128 slots further: those lanes read the array's
+// last four slots instead (a real match or its copy, masked like every lane beyond m) -- 128 more slots per array would be
+// 2 KiB of LDS per workgroup, and at 2000 keypoints that is the difference between two and three workgroups per CU.
 __host__ __device__ constexpr int cnt_pad(int n) { return (n + 255) & ~255; }
+// The word the screen hands on per hypothesis beside pot0: the head's certain inliers (g < lo), kHeadUncertified where
+// nothing of the head is certified, and the sum of the head's cheap values.
+constexpr int kHeadUncertified = -1;
+// relative error of a cheap sum against the sum of its terms: 12 u per term (g against e, see ransac_ties_kernel) and u per
+// float addition on the longest path to the total (`adds`).  2^-18 = 64 u covers 51 additions, i.e. 21 sub-blocks (about
+// 5500 matches); beyond that the term grows with the walk instead of being assumed.
+__device__ __forceinline__ float cnt_sum_rel(int adds) { return fmaxf(0x1p-18f, (float)(13 + adds) * 0x1p-24f); }
 
 struct CntBand {
     float lo, hi;
@@ -459,12 +495,15 @@ __global__ __launch_bounds__(kRankThreads) void ransac_rank_kernel(
     }
 }
 
-// pot0[pair][h] = how many of the kScreenMatches most-missed matches hypothesis h can have as inliers (everything the
-// cheap evaluation does not certify as an outlier).  Workgroup = 128 hypotheses, a wave walks 32 of them with two of the
-// ranked matches per lane.  grid = (ceil(hyp / 128), batch).
+// pot0[pair][h] = how many of the kScreenMatches most-missed matches (the head) hypothesis h can have as inliers (everything
+// the cheap evaluation does not certify as an outlier).  head[pair][h] = (how many of them it certainly has: g < lo, or
+// kHeadUncertified after a zero / denormal / NaN dd; the sum of the head's cheap values): the count kernel starts behind
+// the head with these and evaluates the head again only for a hypothesis that completes with pot0 != certain.
+// Workgroup = 128 hypotheses, a wave walks 32 of them with two of the ranked matches per lane.  grid = (ceil(hyp / 128), batch).
 __global__ __launch_bounds__(256) void ransac_screen_kernel(
     const float *__restrict__ rk, int kp_pad, const int32_t *__restrict__ m_arr, int min_m, int kp_stride, int hyp,
-    float threshold, const float *__restrict__ hypF, const float *__restrict__ cmax, int32_t *__restrict__ pot0) {
+    float threshold, const float *__restrict__ hypF, const float *__restrict__ cmax, const int32_t *__restrict__ cbound,
+    int32_t *__restrict__ pot0, int2 *__restrict__ head) {
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hbase = blockIdx.x * kScreenHyps;
@@ -480,6 +519,7 @@ __global__ __launch_bounds__(256) void ransac_screen_kernel(
         cnt_store_record(s_rec + tid * kCntRec, f, B);
     }
     const int n0 = min(m, kScreenMatches);
+    const int bound_pilots = cbound[b];   // ransac_rank_kernel's: a count some hypothesis of the pair reaches
     const float *r = rk + (size_t)b * 4 * kp_pad;
     const float2 x1 = *reinterpret_cast<const float2 *>(r + 2 * lane);
     const float2 y1 = *reinterpret_cast<const float2 *>(r + kp_pad + 2 * lane);
@@ -490,8 +530,12 @@ __global__ __launch_bounds__(256) void ransac_screen_kernel(
     X2.x = x2.x; X2.y = x2.y; Y2.x = y2.x; Y2.y = y2.y;
     const unsigned long long va = __ballot(2 * lane < n0), vb = __ballot(2 * lane + 1 < n0);
     __syncthreads();
-    int mine = 0;
+    int mine = 0;         // pot0 | certain << 8 (0xFF: not certified) of the hypothesis this lane reports
+    float mine_sum = 0.f;
+    const bool odd1 = (lane & 1) != 0, odd2 = (lane & 2) != 0;
+    const bool in_a = 2 * lane < n0, in_b = 2 * lane + 1 < n0;
     constexpr int kU = 4;   // hypotheses in flight: the record reads and the dependent chain of one hide behind the others
+    static_assert(kU == 4, "the head sums are reduced four hypotheses at a time");
     for (int j = 0; j < 32; j += kU) {
         CntRec R[kU];
         v2f dd[kU], g[kU];
@@ -499,17 +543,48 @@ __global__ __launch_bounds__(256) void ransac_screen_kernel(
         for (int u = 0; u < kU; u++) cnt_load_record(R[u], s_rec, wave * 32 + j + u);
 #pragma unroll
         for (int u = 0; u < kU; u++) g[u] = cnt_cheap(R[u], X1, Y1, X2, Y2, dd[u]);
+        bool any_alive = false;   // wave-uniform: the counts are scalar
 #pragma unroll
         for (int u = 0; u < kU; u++) {
             const unsigned long long oa = __builtin_amdgcn_fcmpf(g[u].x, R[u].hi, kFcmpOGT), ob = __builtin_amdgcn_fcmpf(g[u].y, R[u].hi, kFcmpOGT);
+            const unsigned long long ia = __builtin_amdgcn_fcmpf(g[u].x, R[u].lo, kFcmpOLT), ib = __builtin_amdgcn_fcmpf(g[u].y, R[u].lo, kFcmpOLT);
             int p = __popcll(va & ~oa) + __popcll(vb & ~ob);
+            int c = __popcll(va & ia) + __popcll(vb & ib);
             // a zero / denormal (or NaN) dd: v_rcp_f32 is not a 1-ulp reciprocal there, nothing is certified
-            if (__builtin_amdgcn_fcmpf(fminf(dd[u].x, dd[u].y), kCntTinyDD, kFcmpULT) != 0ull) p = n0;   // unordered or <
-            mine = lane == j + u ? p : mine;
+            if (__builtin_amdgcn_fcmpf(fminf(dd[u].x, dd[u].y), kCntTinyDD, kFcmpULT) != 0ull) {   // unordered or <
+                p = n0;
+                c = 0xFF;
+            }
+            mine = lane == j + u ? (p | (c << 8)) : mine;
+            any_alive = any_alive || p + (m - n0) >= bound_pilots;
         }
+        // The four head sums, reduced together in a fixed order: two exchange steps leave lane l with a partial sum of
+        // hypothesis j + (l & 3), two row rotations and two cross-row exchanges add the 16 lanes of that class.  Lane j + u
+        // is of class u, so it already holds the sum it reports.  Seven additions deep.
+        // (Skipped where none of the four can survive: pot0 + the matches behind the head stays below the pilots' bound, and
+        // the bound only rises from there, so ransac_count_kernel never reads their word.)
+        if (!any_alive) continue;
+        float v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; u++) v[u] = (in_a ? g[u].x : 0.f) + (in_b ? g[u].y : 0.f);
+        const int z = 0;
+        const float k01 = odd1 ? v[1] : v[0], t01 = odd1 ? v[0] : v[1], k23 = odd1 ? v[3] : v[2], t23 = odd1 ? v[2] : v[3];
+        const float r01 = k01 + __int_as_float(__builtin_amdgcn_update_dpp(z, __float_as_int(t01), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+        const float r23 = k23 + __int_as_float(__builtin_amdgcn_update_dpp(z, __float_as_int(t23), 0xB1, 0xF, 0xF, false));
+        const float kk = odd2 ? r23 : r01, tt = odd2 ? r01 : r23;
+        float r = kk + __int_as_float(__builtin_amdgcn_update_dpp(z, __float_as_int(tt), 0x4E, 0xF, 0xF, false));             // quad_perm [2,3,0,1]
+        r += __int_as_float(__builtin_amdgcn_update_dpp(z, __float_as_int(r), 0x124, 0xF, 0xF, false));                       // row_ror:4
+        r += __int_as_float(__builtin_amdgcn_update_dpp(z, __float_as_int(r), 0x128, 0xF, 0xF, false));                       // row_ror:8
+        r += __shfl_xor(r, 16, 64);
+        r += __shfl_xor(r, 32, 64);
+        mine_sum = (lane >> 2) == (j >> 2) ? r : mine_sum;
     }
     const int h = hbase + wave * 32 + lane;
-    if (lane < 32 && h < hyp) pot0[(size_t)b * hyp + h] = mine;
+    if (lane < 32 && h < hyp) {
+        const int c = mine >> 8;
+        pot0[(size_t)b * hyp + h] = mine & 0xFF;
+        head[(size_t)b * hyp + h] = make_int2(c == 0xFF ? kHeadUncertified : c, __float_as_int(mine_sum));
+    }
 }
 
 // The hypotheses that do best on the screen (largest pot0, then one less, first indices, at most kCandMax) are counted in
@@ -651,13 +726,24 @@ __global__ __launch_bounds__(64 * kCandMax) void ransac_cand_kernel(
 }
 
 // grid = (ceil(hyp / 128), batch), block = 512; dynamic LDS = (LDS ? 16 B x cnt_pad(kp_stride) : 0) + 8 queues.
-// LDS = false (more than kCntLdsMatches slots per pair): the ranked coordinates are read from memory instead.
-template <bool LDS>
+// LDS = false (more than kCntLdsMatches matches per pair): the ranked coordinates are read from memory instead.
+// ZERO (experiments build only, VSLAM_RANSAC_COUNT_FROM_ZERO): the walk of before the head start -- every survivor begins
+// at ranked match 0 with nothing seen and takes nothing but its survival from the screen.  For A/B timing and the identity test.
+// exit_payload (a parameter of the experiments build only, VSLAM_RANSAC_COUNT_EXIT_PAYLOAD): the NaN in hyp_sum of an abandoned
+// hypothesis carries the number of matches it had seen -- the histogram of tools/count_exit_hist.py.
+#ifdef VSLAM_EXPERIMENTS
+#define VS_CNT_PAYLOAD_PARAM , int exit_payload
+#define VS_CNT_PAYLOAD_ARG , exit_payload
+#else
+#define VS_CNT_PAYLOAD_PARAM
+#define VS_CNT_PAYLOAD_ARG
+#endif
+template <bool LDS, bool ZERO>
 __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(6, 6))) void ransac_count_kernel(
     const float *__restrict__ rk, int kp_pad, const int32_t *__restrict__ m_arr, int min_m, int kp_stride, int hyp, float threshold,
-    const float *__restrict__ hypF, const int32_t *__restrict__ pot0, const float *__restrict__ cmax,
-    int32_t *__restrict__ hyp_count, float *__restrict__ hyp_sum, float *__restrict__ approx, int32_t *__restrict__ cbound,
-    const unsigned long long *__restrict__ sfloor) {
+    const float *__restrict__ hypF, const int32_t *__restrict__ pot0, const int2 *__restrict__ head,
+    const float *__restrict__ cmax, int32_t *__restrict__ hyp_count, float *__restrict__ hyp_sum, float *__restrict__ approx,
+    int32_t *__restrict__ cbound, const unsigned long long *__restrict__ sfloor VS_CNT_PAYLOAD_PARAM) {
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform, and the compiler may know it
     const int hbase = blockIdx.x * kCntHyps;
@@ -666,8 +752,11 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
     if (m < min_m) return;   // uniform per workgroup
 
     __shared__ __align__(16) float s_rec[kCntHyps * kCntRec];
-    __shared__ int s_cnt[kCntHyps];
-    __shared__ float s_part[kCntHyps];   // sum of the cheap values
+    __shared__ int s_cnt[kCntHyps];      // exact count: starts as the head's certain inliers where the screen's word is taken over
+    __shared__ float s_part[kCntHyps];   // sum of the cheap values: starts as the screen's sum over the head (0 where not certified)
+    // s_state also carries, from bit 2 up, what the screen found: pot0 | kHeadMine (the head has to be evaluated here if the walk
+    // completes) | kHeadNoSum -- a fifth array of 512 B would, at 2000 keypoints, cost the third workgroup per CU
+    constexpr int kHeadMine = 0x10000, kHeadNoSum = 0x20000;
     __shared__ int s_unk[kCntHyps];      // hypothesis whose cheap sum is not certified
     __shared__ int s_state[kCntHyps];    // 0 = ruled out by the screen, 1 = counted in full, 2 = abandoned on the way
     __shared__ int s_list[kCntHyps];     // survivors of the screen: [64 w, 64 w + s_nlist[w]) found by wave w
@@ -679,11 +768,23 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
     const int n0 = min(m, kScreenMatches);
     const int bound0 = cbound[b];   // a count some hypothesis of this pair is known to reach (never above the true maximum)
     if (tid < kCntHyps) {           // whole waves
-        const bool alive = tid < nh && pot0[(size_t)b * hyp + hbase + tid] + (m - n0) >= bound0;
-        s_cnt[tid] = 0;
+        const int p0 = tid < nh ? pot0[(size_t)b * hyp + hbase + tid] : 0;
+        const bool alive = tid < nh && p0 + (m - n0) >= bound0;
+        int certain = 0, word = p0;
+        float hsum = 0.f;
+        if (!ZERO && alive) {
+            // certain == pot0: every evaluation of the head was decided, and decided with a certified band (an
+            // uncertified head reads kHeadUncertified, which no pot0 equals): the head's count is `certain`
+            const int2 hd = head[(size_t)b * hyp + hbase + tid];
+            if (hd.x == p0) certain = hd.x;
+            else word |= kHeadMine;
+            if (hd.x != kHeadUncertified) hsum = __int_as_float(hd.y);
+            else word |= kHeadNoSum;
+        }
+        s_cnt[tid] = certain;
         s_unk[tid] = 0;
-        s_part[tid] = 0.f;
-        s_state[tid] = alive ? 1 : 0;
+        s_part[tid] = hsum;
+        s_state[tid] = (alive ? 1 : 0) | (ZERO ? 0 : word << 2);
         const unsigned long long bal = __ballot(alive);
         if (alive) s_list[wave * 64 + __popcll(bal & ((1ull << lane) - 1ull))] = tid;
         if (lane == 0) s_nlist[wave] = __popcll(bal);
@@ -708,7 +809,7 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
 
     double my_beta = 0;     // thread t < 128 keeps hypothesis t's beta for the bound on its cheap sum
     bool my_ok = false;
-    if (tid < kCntHyps && s_state[tid]) {   // the survivors' records: F, lo, hi
+    if (tid < kCntHyps && (s_state[tid] & 3)) {   // the survivors' records: F, lo, hi
         const float *src = hypF + ((size_t)b * hyp + hbase + tid) * 9;
         float f[9];
 #pragma unroll
@@ -741,8 +842,13 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
         const unsigned long long fkey = sfloor ? sfloor[b] : 0ull;
         const int floor_count = fkey != 0ull ? (int)(fkey >> 32) : -1;
         const float floor_sum = __uint_as_float((uint32_t)fkey);
-        const int nsub = mpad >> 8;
-        const bool part = (m & 255) != 0;
+        // the walk's origin: behind the screen's matches, which every survivor has been evaluated on already
+        const int org = ZERO ? 0 : n0;
+        const int nsub = (m - org + 255) >> 8;
+        const bool part = ((m - org) & 255) != 0;
+        // additions on the longest path to a cheap sum: two per sub-block and lane (the head block included where it is
+        // evaluated here), one across the pair of accumulators, six across the lanes, one for the screen's head sum
+        const float sum_rel = cnt_sum_rel(2 * nsub + 9);
         // the survivors are handed out one at a time: what a hypothesis costs (256 evaluations or all of them) is not known beforehand
         int k = 0;
         if (lane == 0) k = atomicAdd(&s_next, 1);
@@ -759,20 +865,33 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
             bound = max(bound, *(__attribute__((address_space(3))) const volatile int *)&s_bound);
             CntRec R;
             cnt_load_record(R, s_rec, hh);
-            int cnt = 0, pot = 0, seen = 0;
+            // what the screen found on the head: the walk goes on from there (ZERO: nothing is taken over)
+            // (broadcast reads, waited for where they are first used: behind the first block's evaluation)
+            const int word = ZERO ? 0 : s_state[hh] >> 2;
+            const int head_cnt = ZERO ? 0 : *(__attribute__((address_space(3))) const volatile int *)&s_cnt[hh];   // nobody has added to it yet
+            float head_sum = ZERO ? 0.f : s_part[hh];
+            int cnt = 0, pot = word & 0xFFFF, seen = org;
             bool dropped = false, unk = false;
             v2f acc;
             acc.x = 0.f;
             acc.y = 0.f;
-            for (int s = 0; s < nsub; s++) {
+            // Where the screen left something of the head open (an evaluation inside the band, a NaN, an uncertified head),
+            // the head is one more block behind the last: reached only by a walk that completes, evaluated like any other
+            // (the undecided ones queued), its cheap values summed here (the screen's sum is then not added).
+            // (the screen's word is looked at only once the walk is through: the first block's reads do not wait for it)
+            for (int s = 0;; s++) {
+                if (s >= nsub && (ZERO || s > nsub || !(word & kHeadMine))) break;
                 // the lane's four matches of this sub-block: straight from LDS (six waves per SIMD hide the round trip;
                 // fetching a sub-block ahead cost 16 registers and a copy per value)
-                const int ix = s * 256 + 4 * lane;
-                const float4 X1 = *reinterpret_cast<const float4 *>(cx1 + ix), Y1 = *reinterpret_cast<const float4 *>(cy1 + ix);
-                const float4 X2 = *reinterpret_cast<const float4 *>(cx2 + ix), Y2 = *reinterpret_cast<const float4 *>(cy2 + ix);
-                if (s == nsub - 1 && part) {
-                    cnt_sub_block<true>(R, X1, Y1, X2, Y2, ix, hh, lane, m, cnt, q, qn, acc, s_unk, pot, unk);
-                    seen += m & 255;
+                const bool hd = !ZERO && s == nsub;
+                const int pot_walk = pot;
+                const int ix = (hd ? 0 : org + s * 256) + 4 * lane;
+                const int il = min(ix, mpad - 4);   // the arrays end at mpad: lanes beyond it (all beyond m) read its last slots
+                const float4 X1 = *reinterpret_cast<const float4 *>(cx1 + il), Y1 = *reinterpret_cast<const float4 *>(cy1 + il);
+                const float4 X2 = *reinterpret_cast<const float4 *>(cx2 + il), Y2 = *reinterpret_cast<const float4 *>(cy2 + il);
+                if (hd || (s == nsub - 1 && part)) {
+                    cnt_sub_block<true>(R, X1, Y1, X2, Y2, ix, hh, lane, hd ? n0 : m, cnt, q, qn, acc, s_unk, pot, unk);
+                    seen += hd ? 0 : (m - org) & 255;
                 } else {
                     cnt_sub_block<false>(R, X1, Y1, X2, Y2, ix, hh, lane, m, cnt, q, qn, acc, s_unk, pot, unk);
                     seen += 256;
@@ -780,6 +899,11 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
                 while (qn >= 64) {   // a sub-block adds at most 256 words to the 63 left over: kCntQueue holds them
                     cnt_drain(q, qn - 64, 64, lane, s_rec, s_cnt, cx1, cy1, cx2, cy2, threshold);
                     qn -= 64;
+                }
+                if (hd) {
+                    head_sum = 0.f;
+                    pot = pot_walk;   // the head's potential inliers are in pot0 already
+                    break;
                 }
                 // Bail-out.  Even if every match not looked at yet were an inlier, the hypothesis would stay below a
                 // count some hypothesis of this pair is already known to reach: it cannot be a maximum-count hypothesis,
@@ -796,11 +920,12 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
                 // lies below the floor by more than float rounding can close, it is neither the winner nor a tie.
                 // On data with one dominant motion a third to a half of the hypotheses share the maximum count and used to
                 // be counted in full for that; their sums are far from the best one's (outlier residuals dominate them).
-                if (seen < m && bound == floor_count && pot + (m - seen) == bound && !unk && R.beta >= 0.f) {
+                // (The head's share of the cheap sum is the screen's, where the screen certified it.)
+                if (seen < m && bound == floor_count && pot + (m - seen) == bound && !unk && R.beta >= 0.f && !(word & kHeadNoSum)) {
                     // in float, every rounding covered by the 1e-4 factors (the terms are all positive)
-                    const float S = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(acc.x + acc.y)), 63));
+                    const float S = head_sum + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(acc.x + acc.y)), 63));
                     const float ns = (float)seen;
-                    const float err = (2.02f * R.beta * sqrtf(ns * S) + ns * R.beta * R.beta + 0x1p-18f * S) * 1.0001f;
+                    const float err = (2.02f * R.beta * sqrtf(ns * S) + ns * R.beta * R.beta + sum_rel * S) * 1.0001f;
                     const float upper = ((S + err) + threshold * (float)(m - seen)) * 1.0001f;
                     if (upper < floor_sum * 0.9999f) {   // false for NaN
                         dropped = true;
@@ -809,18 +934,44 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
                 }
             }
             if (dropped) {
+#ifdef VSLAM_EXPERIMENTS
+                if (lane == 0) s_state[hh] = 2 | (seen << 2);
+#else
                 if (lane == 0) s_state[hh] = 2;
+#endif
             } else {
-                const float part_sum = wave_sum_to_lane63(acc.x + acc.y);
+                const float part_sum = head_sum + wave_sum_to_lane63(acc.x + acc.y);
+                // The sum rule once more, over the whole walk (nothing is left to assume about matches not seen): a hypothesis
+                // that can at best tie the floor's count with a sum certainly below the floor reports -1 like one abandoned on
+                // the way.  Along a walk an unseen match is charged `threshold` and a seen potential inlier its own cheap value,
+                // so this last use is as a rule the tightest, and which tied hypotheses read -1 then follows from the whole
+                // walk's sum, not from where a sub-block happened to end.  That is not a guarantee (an evaluation inside the
+                // band is charged up to hi, the error term grows with the matches seen, and the cheap sums round differently
+                // in another summation order): a hypothesis within those margins of the floor may read -1 under one block
+                // layout and carry its count under another.  Either is correct: it is beaten on the sum.
+                bool beaten = false;
+                if (bound == floor_count && pot == bound && !unk && R.beta >= 0.f) {
+                    const float S = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part_sum), 63));
+                    const float ns = (float)m;
+                    const float err = (2.02f * R.beta * sqrtf(ns * S) + ns * R.beta * R.beta + sum_rel * S) * 1.0001f;
+                    beaten = (S + err) * 1.0001f < floor_sum * 0.9999f;   // false for NaN
+                }
                 if (lane == 63) s_part[hh] = part_sum;
-                if (lane == 0) {
+                const int certain = head_cnt + cnt;
+                if (beaten) {
+#ifdef VSLAM_EXPERIMENTS
+                    if (lane == 0) s_state[hh] = 2 | (seen << 2);
+#else
+                    if (lane == 0) s_state[hh] = 2;
+#endif
+                } else if (lane == 0) {
                     if (cnt) atomicAdd(&s_cnt[hh], cnt);
-                    if (cnt > bound) {   // the certain inliers alone are a count this hypothesis verifiably reaches
-                        atomicMax(&s_bound, cnt);
-                        atomicMax(&cbound[b], cnt);   // fire and forget: workgroups of this pair that start later begin with it
+                    if (certain > bound) {   // the certain inliers alone are a count this hypothesis verifiably reaches
+                        atomicMax(&s_bound, certain);
+                        atomicMax(&cbound[b], certain);   // fire and forget: workgroups of this pair that start later begin with it
                     }
                 }
-                bound = max(bound, cnt);
+                if (!beaten) bound = max(bound, certain);
             }
             k = __builtin_amdgcn_readfirstlane(knext);
         }
@@ -828,17 +979,23 @@ __global__ __launch_bounds__(64 * kCntWaves) __attribute__((amdgpu_waves_per_eu(
     }
     __syncthreads();
     if (tid < nh) {
-        const int st = s_state[tid];
+        const int st = s_state[tid] & 3;
         hyp_count[out] = st == 1 ? s_cnt[tid] : -1;     // ransac_ties keeps the maximal ones
-        hyp_sum[out] = __int_as_float(0x7FC00000);      // defined by ransac_ties / tiesum where it matters
+        int nan_bits = 0x7FC00000;                      // defined by ransac_ties / tiesum where it matters
+#ifdef VSLAM_EXPERIMENTS
+        if (exit_payload && st != 1) nan_bits |= st == 2 ? min(s_state[tid] >> 2, 0x3FFFFF) : 0x3FFFFF;   // all ones: ruled out by the screen
+#endif
+        hyp_sum[out] = __int_as_float(nan_bits);
         // The cheap values' sum S~ and a bound on |S~ - (exact double sum of the e)|: per evaluation
         // |g - e| <= 12 u max(g, e) + beta (2 sqrt(g) + beta)  (the derivation above), summed with Cauchy-Schwarz
-        // (sum sqrt(g_i) <= sqrt(M sum g_i)), plus 2^-20 S~ for the float additions that formed S~.
-        const float S = s_part[tid];
+        // (sum sqrt(g_i) <= sqrt(M sum g_i)), plus the relative term
+        // (terms and additions: cnt_sum_rel) for the rounding between g and e and the float additions that formed S~.
+        const float S = st == 1 ? s_part[tid] : 0.f;
         float err = INFINITY;
         if (st == 1 && my_ok && !s_unk[tid]) {
             const double Sd = (double)S;
-            err = (float)((2.02 * my_beta * sqrt((double)m * Sd) + (double)m * my_beta * my_beta + 0x1p-18 * Sd) * (1.0 + 0x1p-20));
+            const double rel = (double)cnt_sum_rel(2 * ((m - (ZERO ? 0 : n0) + 255) >> 8) + 9);
+            err = (float)((2.02 * my_beta * sqrt((double)m * Sd) + (double)m * my_beta * my_beta + rel * Sd) * (1.0 + 0x1p-20));
         }
         reinterpret_cast<float2 *>(approx)[out] = make_float2(S, err);
     }
@@ -858,6 +1015,13 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
     unsigned long long *sfloor = nullptr;
     if ((rc = vs_arena_get(ctx, "ransac.sfloor", sizeof(unsigned long long) * (size_t)batch, (void **)&sfloor))) return rc;
     static const bool no_sum_rule = VS_EXPERIMENT_ENV("VSLAM_RANSAC_NO_SUM_RULE") != nullptr;   // A/B timing: bail out on counts only
+    // A/B timing and the identity test: the walk from ranked match 0 (read at every call: a test switches it within a process)
+    const bool from_zero = VS_EXPERIMENT_ENV("VSLAM_RANSAC_COUNT_FROM_ZERO") != nullptr;
+#ifdef VSLAM_EXPERIMENTS
+    const int exit_payload = VS_EXPERIMENT_ENV("VSLAM_RANSAC_COUNT_EXIT_PAYLOAD") != nullptr ? 1 : 0;
+#endif
+    int2 *head = nullptr;
+    if ((rc = vs_arena_get(ctx, "ransac.head", sizeof(int2) * (size_t)batch * hyp, (void **)&head))) return rc;
     const unsigned long long *use_floor = no_sum_rule ? nullptr : sfloor;
     if ((rc = vs_arena_get(ctx, "ransac.pot0", sizeof(int32_t) * (size_t)batch * hyp, (void **)&pot0))) return rc;
     if ((rc = vs_arena_get(ctx, "ransac.rk", sizeof(float) * 4 * (size_t)kp_pad * batch, (void **)&rk))) return rc;
@@ -870,7 +1034,7 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
     {
         VsProfScope ps(ctx, "ransac_screen_kernel");
         dim3 grid(vs_div_up(hyp, kScreenHyps), batch);
-        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, pot0);
+        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head);
     }
     {
         VsProfScope ps(ctx, "ransac_cand_kernel");
@@ -882,17 +1046,35 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
         VsProfScope ps(ctx, "ransac_count_kernel");
         const bool lds = kp_pad <= kCntLdsMatches;
         const size_t dyn = (lds ? sizeof(float) * 4 * (size_t)kp_pad : 0) + sizeof(uint32_t) * kCntQueue * kCntWaves;
-        if (dyn > 32 * 1024 &&   // beyond the default static + dynamic LDS limit
-            (rc = vs_allow_dynamic_lds(ctx, ransac_count_kernel<true>, "ransac_count",
-                                       sizeof(float) * 4 * kCntLdsMatches + sizeof(uint32_t) * kCntQueue * kCntWaves)))
-            return rc;
+        const size_t dyn_max = sizeof(float) * 4 * kCntLdsMatches + sizeof(uint32_t) * kCntQueue * kCntWaves;
         dim3 grid(vs_div_up(hyp, kCntHyps), batch);
+#ifdef VSLAM_EXPERIMENTS
+        if (from_zero) {
+            if (dyn > 32 * 1024 && (rc = vs_allow_dynamic_lds(ctx, ransac_count_kernel<true, true>, "ransac_count_from_zero", dyn_max)))
+                return rc;
+            if (lds)
+                ransac_count_kernel<true, true><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(
+                    rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0, head, cmax, hyp_count, hyp_sum, approx, cbound,
+                    use_floor VS_CNT_PAYLOAD_ARG);
+            else
+                ransac_count_kernel<false, true><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(
+                    rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0, head, cmax, hyp_count, hyp_sum, approx, cbound,
+                    use_floor VS_CNT_PAYLOAD_ARG);
+            return VSLAM_OK;
+        }
+#endif
+        (void)from_zero;
+        if (dyn > 32 * 1024 &&   // beyond the default static + dynamic LDS limit
+            (rc = vs_allow_dynamic_lds(ctx, ransac_count_kernel<true, false>, "ransac_count", dyn_max)))
+            return rc;
         if (lds)
-            ransac_count_kernel<true><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0,
-                                                                                  cmax, hyp_count, hyp_sum, approx, cbound, use_floor);
+            ransac_count_kernel<true, false><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(
+                rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0, head, cmax, hyp_count, hyp_sum, approx, cbound,
+                    use_floor VS_CNT_PAYLOAD_ARG);
         else
-            ransac_count_kernel<false><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0,
-                                                                                   cmax, hyp_count, hyp_sum, approx, cbound, use_floor);
+            ransac_count_kernel<false, false><<<grid, 64 * kCntWaves, dyn, ctx->stream>>>(
+                rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0, head, cmax, hyp_count, hyp_sum, approx, cbound,
+                    use_floor VS_CNT_PAYLOAD_ARG);
     }
     return VSLAM_OK;
 }
