@@ -75,7 +75,26 @@ int vslam_ctx_destroy(vslam_ctx *ctx);
  * since worked on another device -- calls this first.                                                                      */
 int vslam_ctx_make_current(vslam_ctx *ctx);
 /* Borrow a caller-owned hipStream_t (e.g. torch's current stream).  Taken literally: NULL is
- * HIP's default stream.  A fresh context runs on a private non-blocking stream.               */
+ * HIP's default stream.  A fresh context runs on a private non-blocking stream.
+ *
+ * Stream order.  "Stream-ordered" and "asynchronous on the context's stream" mean the same three things for every entry point,
+ * whatever streams of its own the library uses inside (an auxiliary stream for the blur, the rBRIEF table rotation, the k-d
+ * build and the generator's prefetch; a copy stream for vslam_upload_async):
+ *   - device inputs are read no earlier than the work that was queued on the context's stream before the call: a producer
+ *     may queue the kernels that fill them and the entry point on that stream and never stop the host;
+ *   - outputs and resident state (maps, worlds, the context's workspaces) are complete for work queued on that stream after
+ *     the call, and no input is read any more by then: the caller may recycle every array in stream order;
+ *   - host arguments (h_K, h_c1 / h_c2, h_view, the vslam_extract_params and vslam_pose_outputs structs) are consumed before
+ *     the call returns.
+ * The call itself does not wait for the device.  The entry points that do: vslam_ctx_synchronize, vslam_ctx_wait,
+ * vslam_ctx_set_stream (for the stream it leaves), vslam_ctx_destroy, vslam_corner_stats, vslam_prof_count / _enable / _reset
+ * (when timed launches are pending), vslam_copy_h2d, vslam_copy_d2h, vslam_upload_wait (the copy stream only), vslam_dev_free,
+ * vslam_host_free, vslam_map_destroy, vslam_world_destroy, vslam_pipeline_acquire / _submit_* (for the slot's previous batch),
+ * vslam_pipeline_wait / _drain / _destroy -- and any entry point on its first call at a larger shape, when a workspace of the
+ * context has to grow.  vslam_upload_async is the one exception to the first rule: it runs on the copy stream, beside what
+ * is queued, and vslam_upload_fence orders later work behind it.  tests/test_gpu_stream_order.py holds every entry point to
+ * this behind a stalled stream: deterministically where work could start too early, and as far as timing shows it where a
+ * wait for the library's own streams could come too late (they cannot be held back from outside).         */
 int vslam_ctx_set_stream(vslam_ctx *ctx, void *hip_stream);
 /* Waits for the context's stream, then reads AND CLEARS the device-side error word (VSLAM_ERR_CAPACITY if a bounded list
  * overflowed since the last call).  Not for a context that a vslam_pipeline owns: there the word belongs to the ticket in
