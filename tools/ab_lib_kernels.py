@@ -46,8 +46,9 @@ for rnd in range(rounds + 1):
                 acc[which].setdefault(k, []).append(ms / 3)
 print(f"{wl} {kind}: ms per step and kernel slot, A = {sys.argv[1]}, B = {sys.argv[2]}")
 tot = [0.0, 0.0]
-for k in sorted(acc[0], key=lambda k: -np.mean(acc[0][k])):
-    a, b = np.mean(acc[0][k]), np.mean(acc[1].get(k, [float("nan")]))
+# a slot that only one build has (a kernel added or removed between them) counts as 0 ms in the other
+for k in sorted(set(acc[0]) | set(acc[1]), key=lambda k: -np.mean(acc[0].get(k, acc[1].get(k)))):
+    a, b = np.mean(acc[0].get(k, [0.0])), np.mean(acc[1].get(k, [0.0]))
     tot[0] += a
     tot[1] += b
     print(f"{k:28s} {a:8.4f} {b:8.4f} {b - a:+8.4f}")

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Where ransac_count_kernel abandons its hypotheses: a histogram of `matches seen at the exit` on the bench's data, for the
 walk behind the head and (VSLAM_RANSAC_COUNT_FROM_ZERO) the walk from ranked match 0.  Experiments build only: with
-VSLAM_RANSAC_COUNT_EXIT_PAYLOAD the NaN in hyp_sum of an abandoned hypothesis carries the count.
+VSLAM_RANSAC_COUNT_EXIT_PAYLOAD the NaN in hyp_sum of an abandoned hypothesis carries the count.  The walk behind the head is
+taken twice, without ransac_prune (VSLAM_RANSAC_NO_PRUNE) and with it: "pruned" = ruled out before the count kernel with the
+prune kernel and not without it.
     python tools/count_exit_hist.py [C3] [hard|easy]"""
 import os
 import sys
@@ -30,7 +32,11 @@ xy, desc, n = fe["xy"], fe["desc"], fe["n"]
 pairs, m = ctx.match_knn2_ratio(desc[:P].contiguous(), n[:P].contiguous(), desc[P:].contiguous(), n[P:].contiguous())
 sets = ctx.ransac_sets(seeds, m, H)
 os.environ["VSLAM_RANSAC_COUNT_EXIT_PAYLOAD"] = "1"
-for walk in ("behind the head", "from zero"):
+base_early = None   # never walked by the count kernel without the prune kernel
+for walk in ("behind the head, no prune", "behind the head", "from zero"):
+    os.environ.pop("VSLAM_RANSAC_NO_PRUNE", None)
+    if walk == "behind the head, no prune":
+        os.environ["VSLAM_RANSAC_NO_PRUNE"] = "1"
     if walk == "from zero":
         os.environ["VSLAM_RANSAC_COUNT_FROM_ZERO"] = "1"
     out = ctx.ransac_fundamental(xy[:P].contiguous(), xy[P:].contiguous(), pairs, m, sets, 10.0)
@@ -40,12 +46,18 @@ for walk in ("behind the head", "from zero"):
     pay = out["hyp_sum"].cpu().numpy().view(np.uint32) & 0x3FFFFF
     mm = m.cpu().numpy()
     gone = cnt < 0
-    seen = pay[gone]
     tot = cnt.size
     print(f"{wl} {kind}, {walk}: {P} pairs, m mean {mm.mean():.0f}, winner counts mean {out['best'].cpu().numpy()[:, 1].mean():.0f}, "
           f"stage outputs equal the front end's: {same}")
-    print(f"  counted in full {100 * (~gone).sum() / tot:.2f} %   ruled out by the screen {100 * (seen == 0x3FFFFF).sum() / tot:.2f} %")
-    vals, c = np.unique(seen[seen != 0x3FFFFF], return_counts=True)
+    # never walked by the count kernel: the payload is all ones, or none at all where a whole workgroup had nobody left
+    early = gone & ((pay == 0x3FFFFF) | (pay == 0))
+    if base_early is None:
+        base_early = early
+    pruned = early & ~base_early
+    screen = gone & (pay == 0x3FFFFF) & ~pruned
+    print(f"  counted in full {100 * (~gone).sum() / tot:.2f} %   ruled out by the screen {100 * screen.sum() / tot:.2f} %"
+          f"   pruned {100 * pruned.sum() / tot:.2f} %")
+    vals, c = np.unique(pay[gone & ~pruned & (pay != 0x3FFFFF)], return_counts=True)
     rest = 0.0
     for v, k in zip(vals, c):
         if 100 * k / tot >= 0.5 and v % 128 == 0:

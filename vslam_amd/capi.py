@@ -247,6 +247,27 @@ class Context:
                                                 C.c_int(max_corners), C.c_int(max_corners), _ptr(xy), _ptr(n)))
         return xy, n
 
+    def debug_ransac_prune_x(self, batch, hyp):
+        """(experiments build only) X[h] of this context's last ransac_prune launch: the matches behind the ranked head that
+        were certified misses of each hypothesis, (batch, hyp) int32 (zero where no wave walked the hypothesis)."""
+        torch = self.torch
+        x = torch.zeros((batch, hyp), dtype=torch.int32, device="cuda")
+        self._ready()
+        self._check(self.lib.vslam_debug_ransac_prune_x(self.handle, _ptr(x), C.c_int(batch), C.c_int(hyp)))
+        return x
+
+    def debug_ransac_prune_tile(self, F, xy):
+        """(experiments build only) one 32 x 32 tile through ransac_prune's operand and accumulator mapping: F (32, 9), xy (4, 32)
+        = x1, y1, x2, y2 -> n, a0 as (hypothesis, match) f32."""
+        torch = self.torch
+        self._dev(F, torch.float32, "F"); self._dev(xy, torch.float32, "xy")
+        assert tuple(F.shape) == (32, 9) and tuple(xy.shape) == (4, 32)
+        n = torch.zeros((32, 32), dtype=torch.float32, device=F.device)
+        a0 = torch.zeros((32, 32), dtype=torch.float32, device=F.device)
+        self._ready()
+        self._check(self.lib.vslam_debug_ransac_prune_tile(self.handle, _ptr(F), _ptr(xy), _ptr(n), _ptr(a0)))
+        return n, a0
+
     def debug_valu_calib(self):
         self._check(self.lib.vslam_debug_valu_calib(self.handle))
 

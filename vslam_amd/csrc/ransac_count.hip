@@ -1041,6 +1041,9 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
         ransac_cand_kernel<<<batch, 64 * kCandMax, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0,
                                                                      no_sum_rule ? 0 : 1, cbound, sfloor);
     }
+    // cbound is final for the small kernels in front: what certainly stays below it is ruled out on the matrix cores
+    if ((rc = vs_launch_ransac_prune(ctx, rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, batch, kScreenMatches)))
+        return rc;
     if (int arc = vs_aux_job_point(ctx, 4)) return arc;
     {
         VsProfScope ps(ctx, "ransac_count_kernel");

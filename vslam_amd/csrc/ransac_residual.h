@@ -70,3 +70,9 @@ __device__ __forceinline__ v2f residual_e2(const ResidualF &R, const v2f x1, con
 int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, const int32_t *pairs, const int32_t *m,
                            const float *hypF, int batch, int kp_stride, int hyp, float threshold, int32_t *hyp_count,
                            float *hyp_sum, float *approx);
+
+// Between ransac_cand_kernel and ransac_count_kernel (ransac_prune.hip): hypotheses whose certified misses behind the head keep
+// them below cbound get pot0 = -(m - n0) - 1, which ransac_count_kernel reads as "ruled out".  n_head: the screen's matches.
+int vs_launch_ransac_prune(vslam_ctx *ctx, const float *rk, int kp_pad, const int32_t *m, int min_m, int kp_stride, int hyp,
+                           float threshold, const float *hypF, const float *cmax, const int32_t *cbound, int32_t *pot0, int batch,
+                           int n_head);
