@@ -80,9 +80,12 @@ class PointMapModel:
         return offs, od
 
     # ---- every later frame: src/vslam.cpp:69-262
-    def step(self, xy, desc, nodes, image, matches, F, has_model=True):
+    def step(self, xy, desc, nodes, image, matches, F, has_model=True, pose=None):
         """matches: (k, 2) int (first = last frame's keypoint, second = this frame's), F the pair's fundamental matrix as
-        match_features returns them; has_model False = RANSAC accepted no hypothesis."""
+        match_features returns them; has_model False = RANSAC accepted no hypothesis.
+        pose = (R (3, 3), t (3,), c2 (3, 4), points_4d (k, 4)): the values VSLAM_OPT_POSE_REFINE leaves after its adjustment.  They
+        stand in for extract_Rt's, camera_matrix's and triangulate's, so that R_t and pose, the association, the filter and the
+        appended points all use them (include/vslam_amd.h on the option); F is then not read."""
         o = self.o
         frame = Frame(len(self.frames), xy, desc, nodes, self.kp_stride, image)
         last_frame = self.frames[-1]
@@ -92,7 +95,10 @@ class PointMapModel:
             self.stats["growth"].append(0)
             return frame
         matches = np.asarray(matches, np.int32).reshape(-1, 2)
-        R, t = o.extract_Rt(F, self.K)                                                    # :82
+        if pose is not None:
+            R, t = np.asarray(pose[0], np.float32).reshape(3, 3), np.asarray(pose[1], np.float32).reshape(3)
+        else:
+            R, t = o.extract_Rt(F, self.K)                                                # :82
         frame.R_t = np.eye(4, dtype=np.float32)
         frame.R_t[:3, :3] = R
         frame.R_t[:3, 3] = t
@@ -110,7 +116,7 @@ class PointMapModel:
                 self.stats["propagation_pushes"] += 1
         c1 = np.zeros((3, 4), np.float32)
         c1[:, :3] = self.K
-        c2 = o.camera_matrix(self.K, R, t)                                                # :122
+        c2 = o.camera_matrix(self.K, R, t) if pose is None else np.asarray(pose[2], np.float32).reshape(3, 4)   # :122
         if self.size > 0:                                                                  # :126-161
             offs, od = self._csr()
             n = len(frame.points)
@@ -122,7 +128,8 @@ class PointMapModel:
                     self.frame_ids[i].append(frame.id)
                     self.frame_point_ids[i].append(int(claim[i]))
                     self.stats["association_claims"] += 1
-        points_4d = o.triangulate(p1, p2, c1, c2)                                         # :186
+        points_4d = (o.triangulate(p1, p2, c1, c2) if pose is None                        # :186
+                     else np.asarray(pose[3], np.float32).reshape(-1, 4)[:len(matches)])
         inliers, _ = o.reprojection_filter(points_4d, p1, p2, c1, c2, frame.map_point_ids[:max(len(matches), 1)],
                                            thr_sq=self.threshold_sq) if len(matches) else (np.zeros(0, np.int32), 0.0)
         colors = []

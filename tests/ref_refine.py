@@ -119,7 +119,8 @@ def refine(xy1, xy2, matches, K, R_in, t_in, points4d, gate_sq=16.0, max_iterati
     """xy1, xy2 (Kp, 2) f32; matches (n, 2) the compacted inlier matches; R_in (3, 3), t_in (3,), points4d (>= n, 4) f32.
     Returns R (3, 3), t (3,), c2 (3, 4), points4d (copy, refined slots replaced), all float32, and info: stats (4,) as d_stats
     holds them, left_alone, part (n,) bool, objective [accepted values, first = start], marginal, margin, last_rel, eig_ratio,
-    comparable, and the unrounded R64, t64, X64."""
+    comparable, singular (indices within the participating points of the final point blocks that are numerically singular: then
+    eig_ratio is 0 and the run is not comparable), and the unrounded R64, t64, X64."""
     xy1 = np.asarray(xy1, np.float32).astype(np.float64).reshape(-1, 2)
     xy2 = np.asarray(xy2, np.float32).astype(np.float64).reshape(-1, 2)
     Kp = kp_stride if kp_stride is not None else max(len(xy1), len(xy2))
@@ -142,7 +143,7 @@ def refine(xy1, xy2, matches, K, R_in, t_in, points4d, gate_sq=16.0, max_iterati
     def alone():
         return R32.copy(), t32.copy(), c2_in, P32.copy(), dict(
             stats=np.array([cnt, nan, nan, nan]), left_alone=True, part=part, objective=[], marginal=False, margin=np.inf, last_rel=nan,
-            eig_ratio=nan, comparable=False, R64=Ri, t64=ti, X64=X0, o1=o1, o2=o2)
+            eig_ratio=nan, comparable=False, singular=np.zeros(0, np.int64), R64=Ri, t64=ti, X64=X0, o1=o1, o2=o2)
     tn = np.sqrt(ti @ ti)
     if winner < 0 or cnt < 8 or not np.isfinite(ti).all() or not tn > 0:
         return alone()
@@ -230,12 +231,30 @@ def refine(xy1, xy2, matches, K, R_in, t_in, points4d, gate_sq=16.0, max_iterati
     Jc = camera_jacobian(A2, RX, b1, b2)
     V = A1.transpose(0, 2, 1) @ A1 + J2x.transpose(0, 2, 1) @ J2x
     W = Jc.transpose(0, 2, 1) @ J2x
-    S = (Jc.transpose(0, 2, 1) @ Jc).sum(0) - (W @ np.linalg.solve(V, W.transpose(0, 2, 1))).sum(0)
-    ev = np.linalg.eigvalsh(S)
-    ratio = float(ev[0] / ev[-1])
+    # A point that ran off to a depth of 1e9 has a block whose depth direction carries nothing (the loop's damping floor keeps
+    # it solvable there; this undamped one is not): such a run has no determined minimum to compare entries at.
+    singular = singular_blocks(V)
+    ratio = 0.0
+    if len(singular) == 0:
+        try:
+            S = (Jc.transpose(0, 2, 1) @ Jc).sum(0) - (W @ np.linalg.solve(V, W.transpose(0, 2, 1))).sum(0)
+            if np.isfinite(S).all():
+                ev = np.linalg.eigvalsh(S)
+                ratio = float(ev[0] / ev[-1])
+                ratio = ratio if np.isfinite(ratio) else 0.0
+        except np.linalg.LinAlgError:
+            ratio = 0.0
     return Ro, to, c2, P, dict(stats=np.array([cnt, mean_in, mean_out, accepted]), left_alone=False, part=part, objective=history,
                                marginal=bool(margin <= MARGINAL), margin=float(margin), last_rel=float(last_rel), eig_ratio=ratio, comparable=bool(ratio >= EIG_BOUND),
-                               R64=R, t64=t, X64=X, o1=o1, o2=o2)
+                               singular=singular, R64=R, t64=t, X64=X, o1=o1, o2=o2)
+
+
+def singular_blocks(V):
+    """Indices (within the participating points) of the undamped 3 x 3 point blocks that are non-finite or numerically singular
+    in float64: smallest eigenvalue not above 2^-52 of the largest."""
+    fin = np.isfinite(V).all((1, 2))
+    ev = np.linalg.eigvalsh(np.where(fin[:, None, None], V, np.eye(3)))
+    return np.nonzero(~fin | ~(ev[:, 0] > 2.0 ** -52 * ev[:, -1]))[0]
 
 
 def mean_error(K, R, t, X, o1, o2):

@@ -41,38 +41,40 @@ def stack(cases):
     return [np.stack([c[i] for c in cases]) for i in range(1, 8)]
 
 
-def c2_bound(c2):
+def c2_bound(c2, K=KD):
     """c2 is formed from the f64 R and t and rounded once; K [R | t] of the WRITTEN f32 R and t differs by the rounding of c2
     (2^-24 of the largest entry) and by K times the roundings of R and t (entries <= 1: 2^-25 each)."""
-    return 2.0 ** -24 * np.abs(c2).max() + np.abs(KD).sum(1).max() * 2.0 ** -25
+    return 2.0 ** -24 * np.abs(c2).max() + np.abs(K).sum(1).max() * 2.0 ** -25
 
 
-def hold_properties(R, tt, c2, P, st, case, tag):
-    """What every refined (not left alone) output has."""
+def hold_properties(R, tt, c2, P, st, case, tag, K=KD):
+    """What every refined (not left alone) output has.  K: the camera matrix in float64 (the comparison cases' by default)."""
     xy1, xy2, matches, best = case[:4]
     R64, t64 = R.astype(np.float64).reshape(3, 3), tt.astype(np.float64)
     assert np.isfinite(R).all() and np.isfinite(tt).all() and np.isfinite(c2).all(), tag
     assert np.abs(R64.T @ R64 - np.eye(3)).max() <= 2.0 ** -21 and np.linalg.det(R64) > 0, tag
     assert abs(np.sqrt(t64 @ t64) - 1.0) <= 2.0 ** -22, tag
-    want = rr.camera(KD, R64, t64)
-    assert np.abs(c2.astype(np.float64).reshape(3, 4) - want).max() <= c2_bound(c2), tag
-    assert st[2] < st[1], (tag, st)
+    want = rr.camera(K, R64, t64)
+    assert np.abs(c2.astype(np.float64).reshape(3, 4) - want).max() <= c2_bound(c2, K), tag
+    if st is not None:                                          # the pose chain passes no stats pointer
+        assert st[2] < st[1], (tag, st)
     n = int(best[3])
     m = matches[:n]
     inr = (m >= 0).all(1) & (m < len(xy1)).all(1)
     X = P[:n, :3].astype(np.float64)
     ms = np.where(inr[:, None], m, 0)
-    ok, _, _ = rr.participants(KD, R64, t64, X, xy1[ms[:, 0]].astype(np.float64), xy2[ms[:, 1]].astype(np.float64), np.inf)
+    ok, _, _ = rr.participants(K, R64, t64, X, xy1[ms[:, 0]].astype(np.float64), xy2[ms[:, 1]].astype(np.float64), np.inf)
     return ok & inr
 
 
-def hold_to_reference(name, dev, ref, case, delta):
-    R, tt, c2, P, st = dev
+def hold_arrays_to_reference(name, dev, ref, case, delta, st=None, K=KD):
+    """The array part: R, t, c2 and the participating points within tolerance, every other slot's bits kept.  dev = (R, t, c2,
+    points4d); returns the largest err / tol."""
+    R, tt, c2, P = dev[:4]
     Rr, tr, c2r, Pr, info = ref
-    assert st[0] == info["stats"][0], (name, st, info["stats"])
     assert not info["left_alone"] and info["comparable"], name
     part = info["part"]
-    front = hold_properties(R, tt, c2, P, st, case, name)
+    front = hold_properties(R, tt, c2, P, st, case, name, K)
     assert front[part].all(), (name, "every participating point has positive depth in both cameras")
     worst = 0.0
     for nm, a, b, scale in (("R", R.reshape(3, 3), Rr, 1.0), ("t", tt, tr, 1.0), ("c2", c2.reshape(3, 4), c2r, np.abs(c2r).max()),
@@ -84,6 +86,15 @@ def hold_to_reference(name, dev, ref, case, delta):
         assert err <= tol, (name, nm)
     rest = np.ones(len(P), bool); rest[:len(part)][part] = False
     assert np.array_equal(bits(P[rest]), bits(case[6][rest])), (name, "slots of matches that do not participate keep their bits")
+    return worst
+
+
+def hold_to_reference(name, dev, ref, case, delta):
+    R, tt, c2, P, st = dev
+    Rr, tr, c2r, Pr, info = ref
+    assert st[0] == info["stats"][0], (name, st, info["stats"])
+    worst = hold_arrays_to_reference(name, dev, ref, case, delta, st)
+    part = info["part"]
     assert abs(st[1] - info["stats"][1]) <= 1e-9 * info["stats"][1], name
     s2 = rr.mean_error(rr.KMAT, R, tt, P[:len(part)][part, :3], info["o1"][part], info["o2"][part])
     print(f"{name}: stats {st}, ref {info['stats']}, margin {info['margin']:.1e}, worst err / tol {worst:.3f}")

@@ -255,15 +255,18 @@ def sequences():
     return torch.from_numpy(synth.sequences_numpy(2, TRACKS, FRAMES, W, H)).cuda()
 
 
-@pytest.mark.parametrize("refine", [0, 1], ids=["plain", "pose_refine"])
-def test_attached_world_equals_separate_step_and_lift(ctx, sequences, refine):
-    ctx.set_option(ctx.OPT_POSE_REFINE, refine)
+@pytest.mark.parametrize("refit,refine", [(0, 0), (1, 0), (0, 1), (1, 1)], ids=["plain", "pose_refit", "pose_refine", "pose_refit_refine"])
+def test_attached_world_equals_separate_step_and_lift(ctx, sequences, refit, refine):
     a = capi.PointMap(ctx, TRACKS, FRAMES, KP, MCAP, OCAP)
     b = capi.PointMap(ctx, TRACKS, FRAMES, KP, MCAP, OCAP)
     c = capi.PointMap(ctx, TRACKS, FRAMES, KP, MCAP, OCAP)
     wa, wc_ = a.attach_world(), c.attach_world()
     wd = capi.World(ctx, TRACKS, FRAMES, KP)
     try:
+        front = _track(ctx, b, sequences)                         # the front end's outputs with both options off
+        ctx.synchronize()
+        ctx.set_option(ctx.OPT_POSE_REFIT, refit)
+        ctx.set_option(ctx.OPT_POSE_REFINE, refine)
         out = _track(ctx, a, sequences)
         ctx.synchronize()
         sa = a.view()
@@ -278,9 +281,20 @@ def test_attached_world_equals_separate_step_and_lift(ctx, sequences, refine):
         b.reset()
         Km = _Kmat()
         acc = torch.zeros((TRACKS, MCAP, 4), dtype=torch.float32).cuda()
-        last, _ = _frame_batches(out, 0)
+        # VSLAM_OPT_POSE_REFIT is a property of vslam_track_sequences, not of vslam_map_step: by hand, the front end's F is
+        # refitted before the steps
+        own = [t_ * FRAMES + f for t_ in range(TRACKS) for f in range(FRAMES - 1)]
+        for k in ("xy", "desc", "nodes", "n"):
+            assert torch.equal(out[k], front[k]), k
+        for k in ("matches", "best"):
+            assert torch.equal(out[k][own], front[k][own]), k
+        assert torch.equal(out["F"][own], front["F"][own]) == (not refit), "the refit moves F, and nothing else does"
+        last, _ = _frame_batches(front, 0)
         for f in range(1, FRAMES):
-            cur, pair = _frame_batches(out, f)
+            cur, pair = _frame_batches(front, f)
+            if refit:
+                pair["F"], _ = ctx.refit_fundamental(last["xy"], cur["xy"], pair["matches"], pair["best"], pair["F"], want_stats=False)
+                assert torch.equal(pair["F"].view(torch.int32), _frame_batches(out, f)[1]["F"].view(torch.int32)), f
             img = sequences[:, f].contiguous()
             c.step(last, cur, pair, img, Km)
             lo = torch.from_numpy(b.view()["sizes"]).cuda()
@@ -307,6 +321,13 @@ def test_attached_world_equals_separate_step_and_lift(ctx, sequences, refine):
             _track(ctx, a, sequences)
             ctx.synchronize()
             assert not np.array_equal(a.view()["world_Twc"], sa["world_Twc"])
+        if refit:                                                 # and the refitted F
+            ctx.set_option(ctx.OPT_POSE_REFIT, 0)
+            ctx.set_option(ctx.OPT_POSE_REFINE, 0)
+            _track(ctx, a, sequences)
+            ctx.synchronize()
+            assert not np.array_equal(a.view()["world_Twc"], sa["world_Twc"])
+            ctx.set_option(ctx.OPT_POSE_REFINE, refine)           # the render below runs as the steps above did
         # vslam_world_render = vslam_render_points over the world's arrays
         view = capi.View.look_at((-3, -2, -6), (0, 0, 4), (0, 1, 0), 160, 120, lib=ctx.lib, point_size=2)
         wa_arr = wc_.view()
@@ -328,6 +349,7 @@ def test_attached_world_equals_separate_step_and_lift(ctx, sequences, refine):
         assert (e["world_carry_index"] == -1).all() and (e["world_scale"] == 1).all() and (e["world_links"] == 0).all()
         assert np.array_equal(e["world_Twc"], np.tile(np.eye(4).reshape(16), (TRACKS, FRAMES, 1)))
     finally:
+        ctx.set_option(ctx.OPT_POSE_REFIT, 0)
         ctx.set_option(ctx.OPT_POSE_REFINE, 0)
         a.close(); b.close(); c.close()
         wa.close(); wc_.close(); wd.close()

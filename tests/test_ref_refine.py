@@ -74,3 +74,19 @@ def test_accuracy_claim():
     ratios = np.array(ratios)
     print(f"better in {(ratios < 1).sum()} of {len(ratios)}, median {np.median(ratios):.3f}, worst {ratios.max():.3f}")
     assert (ratios < 1).sum() >= 32 - 2
+
+
+def test_singular_point_block_is_reported_not_raised(oracle):
+    """Track 1, pair (0, 1) of the tracking-loop option tests with REFIT and REFINE on, built through the oracle front end
+    (tests/ref_chain.py): three participating points run off to a depth of 5e9 .. 8e9 during the 20 iterations, where the depth
+    direction of their undamped 3 x 3 block carries nothing in float64 (two of the blocks have an exact zero pivot).  The loop's damping floor keeps its own solves regular;
+    the diagnostic after it has no damping and must report such a run, not raise."""
+    import ref_chain as rc
+    bgr, seeds = rc.sequence_inputs()
+    c = rc.pairs_pose(oracle, bgr[1, 0], bgr[1, 1], seeds[1, 0], refit=1, refine=1)
+    info = c["refine_info"]
+    assert not info["left_alone"] and not info["comparable"] and info["eig_ratio"] == 0.0
+    far = np.nonzero(np.abs(info["X64"]).max(1) > 1e8)[0]
+    print(f"|X| of the runaway points: {np.abs(info['X64']).max(1)[far]}, singular {info['singular'].tolist()}")
+    assert len(far) == 3 and np.array_equal(info["singular"], far)
+    assert np.isfinite(c["points4d"]).all() and np.isfinite(c["R"]).all()
