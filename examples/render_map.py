@@ -4,11 +4,13 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world] [output directory]
+    python examples/render_map.py [--world [--resect]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
 and on the right the same points and frusta in one coordinate system (vslam_world_render), seen from the same viewpoint.
+--resect (with --world): every frame's pose is resected against the world's points (include/vslam_resect.h) instead of being
+chained from the pair's fundamental matrix alone; the accepted steps and participants per pair are printed.
 """
 import os
 import sys
@@ -29,8 +31,11 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--world"]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect")]
     with_world = "--world" in sys.argv[1:]
+    resect = "--resect" in sys.argv[1:]
+    if resect and not with_world:
+        sys.exit("--resect needs --world")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -42,7 +47,7 @@ def main():
     bgr = synth.sequences_torch(7, tracks, frames, width, height, dev)
     seeds = torch.arange(tracks * (frames - 1), dtype=torch.int32, device=dev).reshape(tracks, frames - 1).contiguous()
     pmap = capi.PointMap(ctx, tracks, frames, max_corners, map_capacity=frames * max_corners, obs_capacity=4 * frames * max_corners)
-    world = pmap.attach_world() if with_world else None
+    world = pmap.attach_world(resection={} if resect else None) if with_world else None
     # features and matches of every frame and consecutive pair, once (this also runs the whole loop; the map is then rebuilt
     # step by step below so that it can be looked at after every step)
     out = ctx.track_sequences(pmap, bgr, max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
@@ -81,6 +86,10 @@ def main():
     if with_world:
         v = world.view()
         print("scale per pair, track 0:", [round(float(s), 4) for s in v["scale"][0, 1:]], "links:", v["links"][0, 1:].tolist())
+        if resect:
+            st = v["resect_stats"][0, 1:]
+            print("resection, track 0: participants", [int(x) for x in st[:, 0]], "accepted steps",
+                  [None if np.isnan(x) else int(x) for x in st[:, 3]])
     pmap.close()
     if with_world:
         world.close()

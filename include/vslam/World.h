@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../vslam_amd.h"
+#include "../vslam_resect.h"
 
 namespace vslam {
 
@@ -29,6 +30,27 @@ public:
     void step(const int32_t *d_matches, const int32_t *d_best, const float *d_points4d, const float *d_R, const float *d_t,
               const int32_t *d_n_last, const int32_t *d_n_cur) {
         check(vslam_world_step(ctx_, world_, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur), "vslam_world_step");
+    }
+    // Tracking against the map (include/vslam_resect.h), at frame 0 only: from now on the world is stepped with step_resect, which
+    // resects each frame's pose against the carried points.  params: nullptr for the defaults.  clear_resection() undoes it.
+    void set_resection(const vslam_resect_params *params = nullptr) {
+        vslam_resect_params p;
+        check(vslam_resect_params_default(&p), "vslam_resect_params_default");
+        check(vslam_world_set_resection(world_, params ? params : &p), "vslam_world_set_resection");
+    }
+    void clear_resection() { check(vslam_world_set_resection(world_, nullptr), "vslam_world_set_resection"); }
+    // step's arrays, the current frame's keypoints d_xy_cur [tracks][kp_stride][2] and the camera matrix h_K [9] (host, row-major)
+    void step_resect(const int32_t *d_matches, const int32_t *d_best, const float *d_points4d, const float *d_R, const float *d_t,
+                     const int32_t *d_n_last, const int32_t *d_n_cur, const float *d_xy_cur, const float *h_K) {
+        check(vslam_world_step_resect(ctx_, world_, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur, d_xy_cur, h_K),
+              "vslam_world_step_resect");
+    }
+    // [tracks][max_frames][4] f64 on the device: each step's participants, mean rho before / after, accepted steps; nullptr while
+    // resection has never been set
+    double *resection_stats() const {
+        double *d = nullptr;
+        check(vslam_world_resection_view(world_, &d), "vslam_world_resection_view");
+        return d;
     }
     // rows [d_lo, d_hi) per track of the points of pair (frame - 1 -> frame) into d_out; other rows keep their bits
     void lift(int frame, const float *d_points, int stride, const int32_t *d_lo, const int32_t *d_hi, float *d_out) {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../vslam_amd.h"
+#include "../vslam_resect.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -60,6 +61,13 @@ void refit_fundamental(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, c
 void refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const s32 *d_matches, const s32 *d_best, int batch,
                   int kp_stride, const cv::Mat &K, float gate_sq, int max_iterations, float *d_R, float *d_t, float *d_c2,
                   float *d_points4d, f64 *d_stats = nullptr);
+
+// Tracking against the map: the pose-only adjustment of each item's d_R [batch][9] / d_T [batch][3] (f64, in place) from its
+// d_n [batch] correspondences d_points [batch][stride][3] f64 seen at d_xy [batch][stride][2] f32 (vslam_resect_poses,
+// include/vslam_resect.h).  K: 3 x 3 CV_32F; params: nullptr for the defaults.  Stream-ordered on `ctx`; throws
+// std::runtime_error with vslam_last_error on failure.  d_stats [batch][4] f64 or nullptr.
+void resect_poses(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s32 *d_n, int batch, int stride, const cv::Mat &K,
+                  f64 *d_R, f64 *d_T, f64 *d_stats = nullptr, const vslam_resect_params *params = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

@@ -42,6 +42,30 @@ SYMBOLS = [
     "vslam_pipeline_submit_sequence", "vslam_pipeline_poll", "vslam_pipeline_wait", "vslam_pipeline_drain",
 ]
 
+# every symbol include/vslam_resect.h declares (a header of its own beside vslam_amd.h; tests/test_gpu_resect.py checks it)
+RESECT_SYMBOLS = [
+    "vslam_resect_params_default", "vslam_resect_poses", "vslam_world_set_resection", "vslam_world_step_resect",
+    "vslam_world_resection_view",
+]
+
+
+class ResectParams(C.Structure):   # vslam_resect_params
+    _fields_ = [("max_iterations", C.c_int32), ("rounds", C.c_int32), ("min_links", C.c_int32), ("huber_px", C.c_double),
+                ("gate_px", C.c_double)]
+
+    @classmethod
+    def make(cls, lib, **fields):
+        """vslam_resect_params_default with `fields` written over it"""
+        p = cls()
+        rc = lib.vslam_resect_params_default(C.byref(p))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_resect_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"vslam_resect_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
 
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
@@ -379,6 +403,24 @@ class Context:
                                                 Kh.ctypes.data_as(C.c_void_p), C.c_float(gate_sq), C.c_int(max_iterations),
                                                 _ptr(R), _ptr(t), _ptr(c2), _ptr(points4d), _ptr(stats)))
         return R, t, c2, points4d, stats
+
+    def resect_poses(self, points, xy, n, K, R, T, want_stats=True, **params):
+        """vslam_resect_poses (include/vslam_resect.h): the pose-only adjustment of each item's R (B, 9 or 3, 3) f64 and T (B, 3)
+        f64, IN PLACE, from points (B, S, 3) f64 seen at xy (B, S, 2) f32, n (B,) i32 of them; K: the 3 x 3 camera matrix (host);
+        params: fields of vslam_resect_params over its defaults.  Returns (R, T, stats (B, 4) f64 or None)."""
+        import numpy as np
+        torch = self.torch
+        B, S, _ = points.shape
+        for x, dt, nm in ((points, torch.float64, "points"), (xy, torch.float32, "xy"), (n, torch.int32, "n"),
+                          (R, torch.float64, "R"), (T, torch.float64, "T")):
+            self._dev(x, dt, nm)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.empty((B, 4), dtype=torch.float64, device=points.device) if want_stats else None
+        prm = ResectParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_resect_poses(self.handle, _ptr(points), _ptr(xy), _ptr(n), C.c_int(B), C.c_int(S),
+                                                Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(R), _ptr(T), _ptr(stats)))
+        return R, T, stats
 
     def kdtree_build(self, xy, n):
         torch = self.torch
@@ -784,12 +826,16 @@ class PointMap:
             C.c_int(W), C.c_int(H), C.c_int(row_bytes), Kh.ctypes.data_as(C.c_void_p), C.c_float(radius),
             C.c_uint32(dist_threshold), C.c_float(thr_sq)))
 
-    def attach_world(self, world=None, min_links=8):
+    def attach_world(self, world=None, min_links=8, resection=None):
         """vslam_map_attach_world: from now on step() / track_sequences advance `world` (a new World of this map's shape when
         none is given) behind every map step and lift the appended points into its world_points; view() then carries the
-        world's arrays as well.  Returns the world; it is closed after this map, or detached first (detach_world())."""
+        world's arrays as well.  resection: None, or a dict of vslam_resect_params fields ({} for the defaults) set on the
+        world first (World.set_resection): every step then resects the frame's pose against the world's points, with the
+        step's own keypoints and K.  Returns the world; it is closed after this map, or detached first (detach_world())."""
         if world is None:
             world = World(self.ctx, self.tracks, self.max_frames, self.kp_stride, min_links)
+        if resection is not None:
+            world.set_resection(**resection)
         self.ctx._check(self.lib.vslam_map_attach_world(self.handle, world.handle))
         self.world = world
         return world
@@ -868,6 +914,7 @@ class World:
         self.ctx = ctx
         self.lib = ctx.lib
         self.tracks, self.max_frames, self.kp_stride, self.min_links = tracks, max_frames, kp_stride, min_links
+        self.resection = False
         self.handle = C.c_void_p()
         ctx._check(self.lib.vslam_world_create(ctx.handle, C.c_int(tracks), C.c_int(max_frames), C.c_int(kp_stride),
                                                C.c_int(min_links), C.byref(self.handle)))
@@ -875,10 +922,26 @@ class World:
     def reset(self):
         self.ctx._check(self.lib.vslam_world_reset(self.ctx.handle, self.handle))
 
-    def step(self, matches, best, points4d, R, t, n_last, n_cur):
+    def set_resection(self, enable=True, **params):
+        """vslam_world_set_resection (include/vslam_resect.h), allowed at frame 0 only: from now on step() takes xy_cur and K
+        and resects each frame's pose against the carry; params: fields of vslam_resect_params over its defaults.
+        enable=False clears it."""
+        prm = ResectParams.make(self.lib, **params) if enable else None
+        self.ctx._check(self.lib.vslam_world_set_resection(self.handle, C.byref(prm) if enable else C.c_void_p(0)))
+        self.resection = bool(enable)
+
+    def step(self, matches, best, points4d, R, t, n_last, n_cur, xy_cur=None, K=None):
         """vslam_world_step: matches (T, K, 2) i32, best (T, 4) i32, points4d (T, K, 4) f32, R (T, 9) f32, t (T, 3) f32,
-        n_last / n_cur (T,) i32 -- cuda tensors (None is passed on as a null pointer)."""
+        n_last / n_cur (T,) i32 -- cuda tensors (None is passed on as a null pointer).  With xy_cur (T, K, 2) f32 and K (the
+        3 x 3 camera matrix, host): vslam_world_step_resect, the step of a world with resection set."""
         self.ctx._ready()
+        if xy_cur is not None or K is not None:
+            import numpy as np
+            Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9)) if K is not None else None
+            self.ctx._check(self.lib.vslam_world_step_resect(
+                self.ctx.handle, self.handle, _ptr(matches), _ptr(best), _ptr(points4d), _ptr(R), _ptr(t), _ptr(n_last), _ptr(n_cur),
+                _ptr(xy_cur), Kh.ctypes.data_as(C.c_void_p) if Kh is not None else C.c_void_p(0)))
+            return
         self.ctx._check(self.lib.vslam_world_step(self.ctx.handle, self.handle, _ptr(matches), _ptr(best), _ptr(points4d), _ptr(R),
                                                   _ptr(t), _ptr(n_last), _ptr(n_cur)))
 
@@ -914,6 +977,10 @@ class World:
                  carry=get(a.d_carry, (T, Kp, 3), np.float64), carry_index=get(a.d_carry_index, (T, Kp), np.int32))
         if a.d_world_points:
             v["points"] = get(a.d_world_points, (T, int(a.map_capacity), 4), np.float32)
+        stats = C.c_void_p()
+        self.ctx._check(self.lib.vslam_world_resection_view(self.handle, C.byref(stats)))
+        if stats.value:   # PointMap.view() shows it as world_resect_stats
+            v["resect_stats"] = get(stats.value, (T, Fr, 4), np.float64)
         return v
 
     def render(self, pmap, view, width, height, tracks=None, depth=False, row_stride=None, out=None):

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vslam_amd.h"
+#include "../../include/vslam_resect.h"
 
 struct vslam_prof_pending {
     int slot;
@@ -347,6 +348,13 @@ struct vslam_world {
     int map_capacity = 0;
     float *world_points = nullptr;  // [tracks][map_capacity][4]
     int32_t *size_before = nullptr; // [tracks] the map's sizes ahead of the step
+    // vslam_world_set_resection (include/vslam_resect.h): the table the step writes the new carry into (the two change places
+    // after every step) and the per-step statistics; allocated once, when resection is first set
+    bool resect = false;
+    vslam_resect_params resect_params{};
+    double *carry_next = nullptr;        // [tracks][kp_stride][3]
+    int32_t *carry_idx_next = nullptr;   // [tracks][kp_stride]
+    double *resect_stats = nullptr;      // [tracks][max_frames][4]
     std::vector<void *> owned;
 };
 int vs_world_bind(vslam_ctx *ctx, vslam_world *w, int map_capacity);
@@ -354,4 +362,10 @@ int vs_world_bind(vslam_ctx *ctx, vslam_world *w, int map_capacity);
 int vs_world_before_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *sizes);
 int vs_world_after_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *matches, const int32_t *best, const float *points4d,
                             const float *R, const float *t, const int32_t *n_last, const int32_t *n_cur, const float *map_points,
-                            const int32_t *sizes);
+                            const int32_t *sizes, const float *xy_cur, const float *h_K);
+// resect.hip: the resection behind a plain step that wrote frame `fid` and the new carry (carry_next / carry_idx_next)
+int vs_launch_world_resect(vslam_ctx *ctx, vslam_world *w, int fid, const int32_t *matches, const int32_t *best, const float *points4d,
+                           const float *R, const float *t, const int32_t *n_last, const int32_t *n_cur, const float *xy_cur,
+                           const float *h_K);
+int vs_world_resect_reset(vslam_ctx *ctx, vslam_world *w);
+bool vs_resect_params_ok(const vslam_resect_params &p);

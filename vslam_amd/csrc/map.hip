@@ -531,7 +531,7 @@ int map_step(vslam_ctx *ctx, vslam_map *m, const float *xy_last, const uint8_t *
     m->frames = fid + 1;
     // the world frame follows on the step's own R, t and points4d; the rows appended above are lifted
     if (m->world && (rc = vs_world_after_map_step(ctx, m->world, matches, best, m->points4d, m->R, m->t, n_last, n_cur, m->points,
-                                                  m->sizes)))
+                                                  m->sizes, xy_cur, h_K)))
         return rc;
     return VSLAM_OK;
 }

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "ctx.h"
+#include "world_match.h"
 #include "world_select.h"
 
 // the contract's arithmetic is unfused f64, whatever the build's flags are
@@ -30,12 +31,17 @@ struct WorldDev {
     int32_t *links;
     double *carry;
     int32_t *carry_idx;
+    // where the step writes the new carry: the same table, or the second one of a resecting world (include/vslam_resect.h)
+    double *carry_out;
+    int32_t *carry_idx_out;
 };
 
 WorldDev dev_of(const vslam_world *w) {
     WorldDev d;
     d.max_frames = w->max_frames; d.kp_stride = w->kp_stride; d.min_links = w->min_links;
     d.Twc = w->Twc; d.pose = w->pose; d.scale = w->scale; d.links = w->links; d.carry = w->carry; d.carry_idx = w->carry_idx;
+    d.carry_out = w->resect ? w->carry_next : w->carry;
+    d.carry_idx_out = w->resect ? w->carry_idx_next : w->carry_idx;
     return d;
 }
 
@@ -54,29 +60,6 @@ __global__ __launch_bounds__(kWT) void world_reset_kernel(WorldDev w) {
     for (int i = tid; i < 3 * w.kp_stride; i += kWT) w.carry[(size_t)b * w.kp_stride * 3 + i] = 0.0;
 }
 
-struct Match {   // one match under the step's R, t
-    bool usable;   // in range, X and Y finite and in front of both cameras
-    int first, second;
-    double X[3], Y[3];
-};
-
-__device__ __forceinline__ Match load_match(const int2 *__restrict__ M, const float4 *__restrict__ P, int k, int nl, int nc,
-                                            const double *R, const double *t) {
-    Match m;
-    const int2 mt = M[k];
-    m.first = mt.x;
-    m.second = mt.y;
-    m.usable = false;
-    if (!(mt.x >= 0 && mt.x < nl && mt.y >= 0 && mt.y < nc)) return m;   // keypoints the frames hold
-    const float4 p = P[k];   // the stored w is not read
-    m.X[0] = (double)p.x; m.X[1] = (double)p.y; m.X[2] = (double)p.z;
-#pragma unroll
-    for (int r = 0; r < 3; r++) m.Y[r] = ((R[3 * r] * m.X[0] + R[3 * r + 1] * m.X[1]) + R[3 * r + 2] * m.X[2]) + t[r];
-    m.usable = isfinite(m.X[0]) && isfinite(m.X[1]) && isfinite(m.X[2]) && isfinite(m.Y[0]) && isfinite(m.Y[1]) &&
-               isfinite(m.Y[2]) && m.X[2] > 0.0 && m.Y[2] > 0.0;
-    return m;
-}
-
 // dynamic LDS: kp_stride u64 keys; after the selection the same bytes hold kp_stride int32 winners
 __global__ __launch_bounds__(kWT) void world_step_kernel(WorldDev w, int fid, const int32_t *__restrict__ matches,
                                                          const int32_t *__restrict__ best, const float *__restrict__ points4d,
@@ -92,6 +75,8 @@ __global__ __launch_bounds__(kWT) void world_step_kernel(WorldDev w, int fid, co
     const double *Tp = w.Twc + (fr - 1) * 16;
     double *carry = w.carry + (size_t)b * K * 3;
     int32_t *cidx = w.carry_idx + (size_t)b * K;
+    double *carry_out = w.carry_out + (size_t)b * K * 3;
+    int32_t *cidx_out = w.carry_idx_out + (size_t)b * K;
     const double s_prev = w.scale[fr - 1];
     if (best[(size_t)b * 4] < 0) {   // no winner: pose and scale carried over, the carry all invalid
         if (tid < 16) {
@@ -103,7 +88,7 @@ __global__ __launch_bounds__(kWT) void world_step_kernel(WorldDev w, int fid, co
             w.scale[fr] = s_prev;
             w.links[fr] = -1;
         }
-        for (int i = tid; i < K; i += kWT) cidx[i] = -1;
+        for (int i = tid; i < K; i += kWT) cidx_out[i] = -1;
         return;
     }
     const int n = min(max(best[(size_t)b * 4 + 3], 0), K);
@@ -121,7 +106,7 @@ __global__ __launch_bounds__(kWT) void world_step_kernel(WorldDev w, int fid, co
     // links -> keys (slot k of the LDS array belongs to match k; the value of the median does not depend on the slots)
     uint32_t mine = 0;
     for (int k = tid; k < n; k += kWT) {
-        const Match m = load_match(M, P, k, nl, nc, R, t);
+        const VsWorldMatch m = vs_world_load_match(M, P, k, nl, nc, R, t);
         unsigned long long key = kWsNoKey;
         if (m.usable && cidx[m.first] >= 0) {
             const double c[3] = {carry[3 * m.first], carry[3 * m.first + 1], carry[3 * m.first + 2]};
@@ -187,19 +172,19 @@ __global__ __launch_bounds__(kWT) void world_step_kernel(WorldDev w, int fid, co
     for (int i = tid; i < K; i += kWT) win[i] = -1;
     __syncthreads();
     for (int k = tid; k < n; k += kWT) {
-        const Match m = load_match(M, P, k, nl, nc, R, t);
+        const VsWorldMatch m = vs_world_load_match(M, P, k, nl, nc, R, t);
         if (m.usable) atomicMax(&win[m.second], k);
     }
     __syncthreads();
     for (int k = tid; k < n; k += kWT) {
-        const Match m = load_match(M, P, k, nl, nc, R, t);
+        const VsWorldMatch m = vs_world_load_match(M, P, k, nl, nc, R, t);
         if (m.usable && win[m.second] == k) {
-            carry[3 * m.second] = s * m.Y[0];
-            carry[3 * m.second + 1] = s * m.Y[1];
-            carry[3 * m.second + 2] = s * m.Y[2];
+            carry_out[3 * m.second] = s * m.Y[0];
+            carry_out[3 * m.second + 1] = s * m.Y[1];
+            carry_out[3 * m.second + 2] = s * m.Y[2];
         }
     }
-    for (int i = tid; i < K; i += kWT) cidx[i] = win[i];
+    for (int i = tid; i < K; i += kWT) cidx_out[i] = win[i];
 }
 
 // rows [lo, hi) of a track: xf(Twc_(f-1), s_f X) rounded once, w = 1; every lane of a track reads the same Twc and s
@@ -235,7 +220,7 @@ int world_alloc(vslam_ctx *ctx, vslam_world *w, T **out, size_t count) {
 }
 
 int world_step(vslam_ctx *ctx, vslam_world *w, const int32_t *matches, const int32_t *best, const float *points4d, const float *R,
-               const float *t, const int32_t *n_last, const int32_t *n_cur) {
+               const float *t, const int32_t *n_last, const int32_t *n_cur, const float *xy_cur = nullptr, const float *h_K = nullptr) {
     int rc;
     if (w->frames >= w->max_frames) {   // no slot for this frame: nothing happens to any track
         int32_t *errflag = nullptr;
@@ -253,6 +238,11 @@ int world_step(vslam_ctx *ctx, vslam_world *w, const int32_t *matches, const int
         world_step_kernel<<<w->tracks, kWT, lds, ctx->stream>>>(dev_of(w), w->frames, matches, best, points4d, R, t, n_last, n_cur);
     }
     VS_HIP(ctx, hipGetLastError());
+    if (w->resect) {   // the resection reads the old carry and the step's s0, then the two carry tables change places
+        if ((rc = vs_launch_world_resect(ctx, w, w->frames, matches, best, points4d, R, t, n_last, n_cur, xy_cur, h_K))) return rc;
+        std::swap(w->carry, w->carry_next);
+        std::swap(w->carry_idx, w->carry_idx_next);
+    }
     w->frames += 1;
     return VSLAM_OK;
 }
@@ -288,10 +278,10 @@ int vs_world_before_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *size
 
 int vs_world_after_map_step(vslam_ctx *ctx, vslam_world *w, const int32_t *matches, const int32_t *best, const float *points4d,
                             const float *R, const float *t, const int32_t *n_last, const int32_t *n_cur, const float *map_points,
-                            const int32_t *sizes) {
+                            const int32_t *sizes, const float *xy_cur, const float *h_K) {
     const int fid = w->frames;
     int rc;
-    if ((rc = world_step(ctx, w, matches, best, points4d, R, t, n_last, n_cur))) return rc;
+    if ((rc = world_step(ctx, w, matches, best, points4d, R, t, n_last, n_cur, xy_cur, h_K))) return rc;
     if (w->frames == fid) return VSLAM_OK;   // beyond max_frames: reported, nothing to lift
     return world_lift(ctx, w, fid, map_points, w->map_capacity, w->size_before, sizes, w->world_points);
 }
@@ -317,6 +307,7 @@ int vslam_world_reset(vslam_ctx *ctx, vslam_world *world) {
     world_reset_kernel<<<world->tracks, kWT, 0, ctx->stream>>>(dev_of(world));
     VS_HIP(ctx, hipGetLastError());
     world->frames = 1;
+    if (world->resect_stats) return vs_world_resect_reset(ctx, world);
     return VSLAM_OK;
 }
 
@@ -356,7 +347,53 @@ int vslam_world_step(vslam_ctx *ctx, vslam_world *world, const int32_t *d_matche
     VS_ALIGNED(ctx, d_matches, 8);      // int2 rows
     VS_ALIGNED(ctx, d_points4d, 16);    // float4 rows
     VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_R, d_t, d_n_last, d_n_cur) % 4 == 0, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, !world->resect, VSLAM_ERR_INVALID);   // a resecting world is stepped by vslam_world_step_resect
     return world_step(ctx, world, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur);
+}
+
+int vslam_world_step_resect(vslam_ctx *ctx, vslam_world *world, const int32_t *d_matches, const int32_t *d_best,
+                            const float *d_points4d, const float *d_R, const float *d_t, const int32_t *d_n_last,
+                            const int32_t *d_n_cur, const float *d_xy_cur, const float *h_K) {
+    if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, world && world->ctx == ctx, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, d_matches && d_best && d_points4d && d_R && d_t && d_n_last && d_n_cur && d_xy_cur && h_K, VSLAM_ERR_INVALID);
+    VS_ALIGNED(ctx, d_matches, 8);
+    VS_ALIGNED(ctx, d_points4d, 16);
+    VS_ALIGNED(ctx, d_xy_cur, 8);       // float2 rows
+    VS_REQUIRE(ctx, vs_ptr_bits(d_best, d_R, d_t, d_n_last, d_n_cur) % 4 == 0, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, world->resect, VSLAM_ERR_INVALID);
+    return world_step(ctx, world, d_matches, d_best, d_points4d, d_R, d_t, d_n_last, d_n_cur, d_xy_cur, h_K);
+}
+
+int vslam_world_set_resection(vslam_world *world, const vslam_resect_params *params) {
+    if (!world || !world->ctx) return VSLAM_ERR_INVALID;
+    vslam_ctx *ctx = world->ctx;
+    VS_REQUIRE(ctx, world->frames == 1, VSLAM_ERR_INVALID);   // between two steps the carry of the last one is in use
+    if (!params) {
+        world->resect = false;
+        return VSLAM_OK;
+    }
+    VS_REQUIRE(ctx, vs_resect_params_ok(*params), VSLAM_ERR_INVALID);
+    if (!world->resect_stats) {
+        const size_t T = world->tracks, K = world->kp_stride;
+        int rc = world_alloc(ctx, world, &world->carry_next, T * K * 3);
+        if (rc == VSLAM_OK) rc = world_alloc(ctx, world, &world->carry_idx_next, T * K);
+        if (rc == VSLAM_OK) rc = world_alloc(ctx, world, &world->resect_stats, T * world->max_frames * 4);
+        if (rc == VSLAM_OK) rc = vs_world_resect_reset(ctx, world);
+        if (rc != VSLAM_OK) {
+            world->resect_stats = nullptr;   // freed with the world
+            return rc;
+        }
+    }
+    world->resect_params = *params;
+    world->resect = true;
+    return VSLAM_OK;
+}
+
+int vslam_world_resection_view(vslam_world *world, double **d_stats) {
+    if (!world || !d_stats) return VSLAM_ERR_INVALID;
+    *d_stats = world->resect_stats;
+    return VSLAM_OK;
 }
 
 int vslam_world_lift(vslam_ctx *ctx, vslam_world *world, int frame, const float *d_points, int stride, const int32_t *d_lo,

@@ -854,6 +854,15 @@ void refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const 
                                       d_c2, d_points4d, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_refine_pairs: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void resect_poses(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s32 *d_n, int batch, int stride, const cv::Mat &K,
+                  f64 *d_R, f64 *d_T, f64 *d_stats, const vslam_resect_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("resect_poses: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_resect_poses(ctx, d_points, d_xy, d_n, batch, stride, k, params, d_R, d_T, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_resect_poses: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
