@@ -4,13 +4,15 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect]] [output directory]
+    python examples/render_map.py [--world [--resect] [--adjust]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
 and on the right the same points and frusta in one coordinate system (vslam_world_render), seen from the same viewpoint.
 --resect (with --world): every frame's pose is resected against the world's points (include/vslam_resect.h) instead of being
 chained from the pair's fundamental matrix alone; the accepted steps and participants per pair are printed.
+--adjust (with --world): after the last step the last window of 8 frames and the points they observe are adjusted together
+(World.adjust, include/vslam_adjust.h) and the world is drawn once more: track*_before_adjust.ppm / track*_after_adjust.ppm.
 """
 import os
 import sys
@@ -31,11 +33,12 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
-    if resect and not with_world:
-        sys.exit("--resect needs --world")
+    adjust = "--adjust" in sys.argv[1:]
+    if (resect or adjust) and not with_world:
+        sys.exit("--resect and --adjust need --world")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -90,6 +93,18 @@ def main():
             st = v["resect_stats"][0, 1:]
             print("resection, track 0: participants", [int(x) for x in st[:, 0]], "accepted steps",
                   [None if np.isnan(x) else int(x) for x in st[:, 3]])
+        if adjust:
+            world.render(pmap, view, W, H, out=(world_images, None))
+            before = world_images.cpu().numpy()
+            st = world.adjust(pmap, out["xy"], K, window=8).cpu().numpy()
+            world.render(pmap, view, W, H, out=(world_images, None))
+            ctx.synchronize()
+            after = world_images.cpu().numpy()
+            for t in range(tracks):
+                write_ppm(os.path.join(out_dir, f"track{t}_before_adjust.ppm"), before[t])
+                write_ppm(os.path.join(out_dir, f"track{t}_after_adjust.ppm"), after[t])
+            print("adjustment per track: participants", [int(x) for x in st[:, 0]], "mean rho", [round(float(x), 3) for x in st[:, 1]], "->",
+                  [round(float(x), 3) for x in st[:, 2]], "accepted steps", [None if np.isnan(x) else int(x) for x in st[:, 3]])
     pmap.close()
     if with_world:
         world.close()

@@ -9,6 +9,7 @@
 
 #include "../vslam_amd.h"
 #include "../vslam_resect.h"
+#include "../vslam_adjust.h"
 
 namespace vslam {
 
@@ -66,6 +67,13 @@ public:
                 uint8_t *d_bgr_out, float *d_depth_out = nullptr) {
         check(vslam_world_render(ctx_, world_, map, track_lo, track_count, &view, width, height, row_stride, d_bgr_out, d_depth_out),
               "vslam_world_render");
+    }
+    // The last `window` frames of every track and the map points they observe adjusted together, in place (vslam_world_adjust,
+    // include/vslam_adjust.h).  The world must be the one attached to `map`; d_xy [tracks * xy_frames][kp_stride][2] as
+    // vslam_track_sequences leaves it; params: nullptr for the defaults; d_stats [tracks][4] f64 or nullptr.
+    void adjust(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, int window = 8,
+                const vslam_adjust_params *params = nullptr, double *d_stats = nullptr) {
+        check(vslam_world_adjust(ctx_, world_, map, d_xy, xy_frames, h_K, window, params, d_stats), "vslam_world_adjust");
     }
     vslam_world *handle() const { return world_; }
 

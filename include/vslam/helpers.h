@@ -7,6 +7,7 @@
 
 #include "../vslam_amd.h"
 #include "../vslam_resect.h"
+#include "../vslam_adjust.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -68,6 +69,13 @@ void refine_pairs(vslam_ctx *ctx, const float *d_xy1, const float *d_xy2, const 
 // std::runtime_error with vslam_last_error on failure.  d_stats [batch][4] f64 or nullptr.
 void resect_poses(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s32 *d_n, int batch, int stride, const cv::Mat &K,
                   f64 *d_R, f64 *d_T, f64 *d_stats = nullptr, const vslam_resect_params *params = nullptr);
+
+// A window of cameras and the points they share adjusted together, for a batch of items the caller holds on the device
+// (vslam_adjust_windows, include/vslam_adjust.h: the arrays and strides are that call's).  K: 3 x 3 CV_32F; params: nullptr for
+// the defaults; d_stats [batch][4] f64 or nullptr.  Stream-ordered on `ctx`; throws std::runtime_error with vslam_last_error.
+void adjust_windows(vslam_ctx *ctx, f64 *d_R, f64 *d_T, const s32 *d_n_cams, int cam_stride, f64 *d_points, const s32 *d_n_points,
+                    int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const float *d_obs_xy, int obs_stride, int batch,
+                    const cv::Mat &K, f64 *d_stats = nullptr, const vslam_adjust_params *params = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

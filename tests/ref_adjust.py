@@ -1,0 +1,501 @@
+"""The window adjustment (include/vslam_adjust.h: vslam_adjust_windows) restated in numpy float64, written from the header's text
+-- not from the device code.  Nothing is fused: one IEEE operation per Python operator, in the header's order.  The per-observation
+arithmetic is written once over arrays (the same operations element by element); a point's sums over its observations are
+np.bincount's (sequential, in CSR order: the header's), sums over the POINTS are numpy's (pairwise), which is NOT the device's
+order, and the reduced solve's inner sums are numpy dot products: those differences, and the library sine, are what the device
+comparison's tolerance is for.
+
+adjust()                the adjustment of one item.
+problem()               synthetic items: an exact scene, keypoints rounded to f32, free cameras and points perturbed.
+second_formulation()    the same objective over the last round's participants through scipy.optimize.least_squares(loss="huber",
+                        f_scale=delta), one residual e = |r| per observation (scipy applies its loss per residual: with the norm as
+                        the residual, rho(e) is exactly the header's), a rotation vector and T per free camera and every
+                        participating point as unknowns, the Jacobian by sparse 3-point differences, started from adjust()'s result.
+
+Measured here on the CPU (tests/test_ref_adjust.py re-measures and compares):
+  DELTA_REF = 1.1e-10: the largest disagreement() over DELTA_REF_CASES (per case below, beside DELTA_REF).
+  exact problems (problem(seed, 6, 120, seen=1.0), outliers 0 and 0.2): error of the camera centres and the participating points /
+  (2^-23 max|X|) per seed in MEASURED_RATIOS / MEASURED_RATIOS_OUTLIERS; C_BOUND = 4 x the largest.  The start is off by
+  0.02 in the centres and 0.05 in the points: four orders of magnitude more.  With seen=0.8 three of six seeds did not come back at outliers 0.2, and before
+  problem() kept a true majority per point six of ten: see problem().
+Nothing about real footage has been measured.
+"""
+import numpy as np
+
+import ref_resect as rr
+import ref_world as rw
+
+f64 = np.float64
+LAMBDA0, LAMBDA_MIN, LAMBDA_MAX, REL_STOP, DIAG_FLOOR = rr.LAMBDA0, rr.LAMBDA_MIN, rr.LAMBDA_MAX, rr.REL_STOP, rr.DIAG_FLOOR
+DECIDED_MARGIN = rr.DECIDED_MARGIN   # every accept / refuse decision of a run at least this far from a tie: the run is DECIDED
+MAX_CAMS = 8
+DEFAULTS = dict(max_iterations=20, rounds=3, min_obs=8, n_fixed=2, huber_px=2.0, gate_px=6.0)
+kmat = rr.kmat
+
+
+def params(**kw):
+    p = dict(DEFAULTS)
+    p.update(kw)
+    return p
+
+
+# ------------------------------------------------------------------------------------------------ pieces of the contract
+def observe(K, R, T, X, pid, cam, xy):
+    """per observation: RX (m, 3), Y (m, 3), u, v, q2, r0, r1, e under cameras R (C, 9), T (C, 3) and points X (N, 3)"""
+    Rk, Tk, P = R[cam], T[cam], X[pid]
+    RX = np.stack([(Rk[:, 3 * r] * P[:, 0] + Rk[:, 3 * r + 1] * P[:, 1]) + Rk[:, 3 * r + 2] * P[:, 2] for r in range(3)], 1)
+    Y = RX + Tk
+    u, v, q2 = rr.project(K, Y)
+    r0, r1 = u - xy[:, 0], v - xy[:, 1]
+    with np.errstate(all="ignore"):
+        e = np.sqrt(r0 * r0 + r1 * r1)
+    return RX, Y, u, v, q2, r0, r1, e
+
+
+def blocks(K, R, T, X, pid, cam, xy, delta):
+    """per observation: V (m, 6: 00 01 02 11 12 22), gx (m, 3), U (m, 21), gc (m, 6), W (m, 6, 3)"""
+    RX, Y, u, v, q2, r0, r1, e = observe(K, R, T, X, pid, cam, xy)
+    Rk = R[cam]
+    with np.errstate(all="ignore"):
+        A = [[(K[k] - u * K[6 + k]) / q2 for k in range(3)], [(K[3 + k] - v * K[6 + k]) / q2 for k in range(3)]]
+        Jx = [[(A[r][0] * Rk[:, k] + A[r][1] * Rk[:, 3 + k]) + A[r][2] * Rk[:, 6 + k] for k in range(3)] for r in range(2)]
+        Jc = []
+        for r in range(2):
+            a = A[r]
+            Jc.append([a[2] * RX[:, 1] - a[1] * RX[:, 2], a[0] * RX[:, 2] - a[2] * RX[:, 0], a[1] * RX[:, 0] - a[0] * RX[:, 1], a[0], a[1], a[2]])
+        w = np.where(e <= delta, 1.0, delta / e)
+        m = len(pid)
+        V, gx, U, gc, W = np.empty((m, 6)), np.empty((m, 3)), np.empty((m, 21)), np.empty((m, 6)), np.empty((m, 6, 3))
+        t = 0
+        for i in range(3):
+            for j in range(i, 3):
+                V[:, t] = w * (Jx[0][i] * Jx[0][j] + Jx[1][i] * Jx[1][j]); t += 1
+            gx[:, i] = w * (Jx[0][i] * r0 + Jx[1][i] * r1)
+        for i in range(6):
+            for j in range(3):
+                W[:, i, j] = w * (Jc[0][i] * Jx[0][j] + Jc[1][i] * Jx[1][j])
+            for j in range(i, 6):
+                U[:, rr.tri(i, j)] = w * (Jc[0][i] * Jc[0][j] + Jc[1][i] * Jc[1][j])
+            gc[:, i] = w * (Jc[0][i] * r0 + Jc[1][i] * r1)
+    return V, gx, U, gc, W
+
+
+def _seq(idx, vals, n):
+    """sum of vals (m, ...) per index, sequentially in the order given -> (n, ...)"""
+    flat = vals.reshape(len(vals), -1)
+    out = np.stack([np.bincount(idx, flat[:, k], n) for k in range(flat.shape[1])], 1) if len(vals) else np.zeros((n, flat.shape[1]))
+    return out.reshape((n,) + vals.shape[1:])
+
+
+def chol3(V, lam):
+    """V (n, 6) -> L entries and ok (n,)"""
+    with np.errstate(all="ignore"):
+        v00 = V[:, 0] + lam * np.maximum(V[:, 0], DIAG_FLOOR)
+        v11 = V[:, 3] + lam * np.maximum(V[:, 3], DIAG_FLOOR)
+        v22 = V[:, 5] + lam * np.maximum(V[:, 5], DIAG_FLOOR)
+        l00 = np.sqrt(v00); l10 = V[:, 1] / l00; l20 = V[:, 2] / l00
+        d1 = v11 - l10 * l10
+        l11 = np.sqrt(d1); l21 = (V[:, 4] - l20 * l10) / l11
+        d2 = (v22 - l20 * l20) - l21 * l21
+        l22 = np.sqrt(d2)
+    return (l00, l10, l20, l11, l21, l22), (v00 > 0) & (d1 > 0) & (d2 > 0)
+
+
+def solve3(L, b):
+    """(L L^t) y = b for b (n, ..., 3): by L then L^t"""
+    l00, l10, l20, l11, l21, l22 = [x.reshape((-1,) + (1,) * (b.ndim - 2)) for x in L]
+    with np.errstate(all="ignore"):
+        f0 = b[..., 0] / l00
+        f1 = (b[..., 1] - l10 * f0) / l11
+        f2 = ((b[..., 2] - l20 * f0) - l21 * f1) / l22
+        y2 = f2 / l22
+        y1 = (f1 - l21 * y2) / l11
+        y0 = ((f0 - l10 * y1) - l20 * y2) / l00
+    return np.stack([y0, y1, y2], -1)
+
+
+def reduced_solve(S, Ud, rhs, lam):
+    """(S + lam max(Ud, floor) on the diagonal) dc = -rhs by Cholesky -> dc or None"""
+    n = len(rhs)
+    L = np.zeros((n, n))
+    with np.errstate(all="ignore"):
+        for j in range(n):
+            p = (S[j, j] + lam * max(Ud[j], DIAG_FLOOR)) - float(L[j, :j] @ L[j, :j])
+            if not p > 0.0:
+                return None
+            L[j, j] = np.sqrt(p)
+            L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+        f = np.zeros(n)
+        for i in range(n):
+            f[i] = (rhs[i] - L[i, :i] @ f[:i]) / L[i, i]
+        d = np.zeros(n)
+        for i in range(n - 1, -1, -1):
+            d[i] = (f[i] - L[i + 1:, i] @ d[i + 1:]) / L[i, i]
+    return -d if np.isfinite(d).all() else None
+
+
+def step(K, R, T, X, pid, cam, xy, slot, delta, lam, plant=None):
+    """One damped step over the observations given (all of them participants): -> (dc (6 F,), dX (N, 3), touched (N,) bool) or None.
+    slot (C,): the slot of each camera or -1."""
+    N, F = len(X), int(slot.max()) + 1
+    V_o, gx_o, U_o, gc_o, W_o = blocks(K, R, T, X, pid, cam, xy, delta)
+    V, gx = _seq(pid, V_o, N), _seq(pid, gx_o, N)
+    touched = np.bincount(pid, minlength=N) > 0
+    fr = slot[cam] >= 0
+    key = pid[fr] * F + slot[cam][fr]
+    has = np.bincount(key, minlength=N * F).reshape(N, F) > 0
+    W = _seq(key, W_o[fr], N * F).reshape(N, F, 6, 3)
+    U = _seq(key, U_o[fr], N * F).reshape(N, F, 21)
+    gc = _seq(key, gc_o[fr], N * F).reshape(N, F, 6)
+    t = touched
+    L, ok = chol3(V[t], lam)
+    if not ok.all():
+        return None
+    z = np.zeros((N, 3)); Y = np.zeros((N, F, 6, 3))
+    z[t] = solve3(L, gx[t])
+    Y[t] = solve3(L, W[t])
+    n = 6 * F
+    S, Ud, rhs = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+    dot = lambda a, b: (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+    for s in range(F):
+        hs = has[:, s]
+        for j in range(6):
+            rhs[6 * s + j] = (gc[hs, s, j] - dot(W[hs, s, j], z[hs])).sum()
+            Ud[6 * s + j] = U[hs, s, rr.tri(j, j)].sum()
+            for l in range(j, 6):
+                yw = 0.0 if plant == "schur_dropped" else dot(Y[hs, s, j], W[hs, s, l])
+                S[6 * s + l, 6 * s + j] = S[6 * s + j, 6 * s + l] = (U[hs, s, rr.tri(j, l)] - yw).sum()
+        for s2 in range(s + 1, F):
+            both = hs & has[:, s2]
+            if plant == "schur_dropped":
+                continue
+            for j in range(6):
+                for l in range(6):
+                    S[6 * s2 + l, 6 * s + j] = S[6 * s + j, 6 * s2 + l] = (-dot(Y[both, s, j], W[both, s2, l])).sum()
+    dc = reduced_solve(S, Ud, rhs, lam)
+    if dc is None:
+        return None
+    acc = z.copy()
+    for s in range(F):
+        hs = has[:, s]
+        yd = Y[hs, s, 0] * dc[6 * s]
+        for j in range(1, 6):
+            yd = yd + Y[hs, s, j] * dc[6 * s + j]
+        acc[hs] = acc[hs] + yd
+    dX = -acc
+    if not np.isfinite(dX[t]).all():
+        return None
+    return dc, dX, touched
+
+
+def dense_step(K, R, T, X, pid, cam, xy, slot, delta, lam):
+    """the same step from the full damped normal equations (J^t W J + lam max(diag, floor)) d = -J^t W r by numpy's solver"""
+    N, F = len(X), int(slot.max()) + 1
+    RX, Y, u, v, q2, r0, r1, e = observe(K, R, T, X, pid, cam, xy)
+    w = np.where(e <= delta, 1.0, delta / e)
+    m, n = len(pid), 6 * F + 3 * N
+    J = np.zeros((2 * m, n)); r = np.zeros(2 * m); ww = np.repeat(w, 2)
+    for k in range(m):
+        c = cam[k]
+        A = np.array([[(K[j] - u[k] * K[6 + j]) / q2[k] for j in range(3)], [(K[3 + j] - v[k] * K[6 + j]) / q2[k] for j in range(3)]])
+        x = RX[k]
+        skew = np.array([[0, -x[2], x[1]], [x[2], 0, -x[0]], [-x[1], x[0], 0]])
+        if slot[c] >= 0:
+            J[2 * k:2 * k + 2, 6 * slot[c]:6 * slot[c] + 6] = A @ np.hstack([-skew, np.eye(3)])
+        J[2 * k:2 * k + 2, 6 * F + 3 * pid[k]:6 * F + 3 * pid[k] + 3] = A @ R[c].reshape(3, 3)
+        r[2 * k], r[2 * k + 1] = r0[k], r1[k]
+    H = J.T @ (ww[:, None] * J)
+    g = J.T @ (ww * r)
+    used = np.concatenate([np.ones(6 * F, bool), np.repeat(np.bincount(pid, minlength=N) > 0, 3)])
+    H = H + np.diag(lam * np.maximum(np.diag(H), DIAG_FLOOR))
+    d = np.zeros(n)
+    d[used] = np.linalg.solve(H[np.ix_(used, used)], -g[used])
+    return d[:6 * F], d[6 * F:].reshape(N, 3)
+
+
+# ------------------------------------------------------------------------------------------------ the header's algorithm
+def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
+    """R_in (C, 9), T_in (C, 3), X_in (N, 3) f64; off (N + 1,), cam (m,) int; xy (m, 2) f32; K 3 x 3 f32.
+    -> R, T, X, stats (4,), info.  Left alone: the inputs' bits.  info: moved, part (m,) bool (the last round's participants),
+    free (C,) bool (free in some round), took_part (N,) bool (in some round; only the last round's points are written), margin (the closest accept / refuse decision to a
+    tie: |new / old - 1|), gate_margin (the closest gate decision: |e / gate - 1|), objective (accepted values per round)."""
+    p = params(**kw)
+    R0, T0, X0 = np.array(R_in, f64).reshape(-1, 9), np.array(T_in, f64).reshape(-1, 3), np.array(X_in, f64).reshape(-1, 3)
+    off, cam = np.asarray(off, np.int64), np.asarray(cam, np.int64)
+    xy = np.asarray(xy, np.float32).astype(f64).reshape(-1, 2)
+    K = np.asarray(K, np.float32).astype(f64).reshape(9)
+    C, N = len(R0), len(X0)
+    nan = float("nan")
+    info = dict(moved=False, part=np.zeros(len(cam), bool), free=np.zeros(C, bool), took_part=np.zeros(N, bool), margin=np.inf,
+                gate_margin=np.inf, objective=[])
+
+    def alone(count):
+        return R0.copy(), T0.copy(), X0.copy(), np.array([count, nan, nan, nan]), info
+    if not (1 <= C <= MAX_CAMS) or len(off) != N + 1 or off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > len(cam):
+        return alone(0)
+    if not (np.isfinite(K).all() and np.isfinite(R0).all() and np.isfinite(T0).all()):
+        return alone(0)
+    m = int(off[-1])
+    cam, xy = cam[:m], xy[:m]
+    pid = np.repeat(np.arange(N), np.diff(off))
+    delta, gate = f64(p["huber_px"]), f64(p["gate_px"])
+    nf = 0 if plant == "fixed_moves" else p["n_fixed"]
+    Rs = R0.copy()
+    for c in range(p["n_fixed"], C):
+        Rs[c] = rr.start_rotation(R0[c])
+    R, T, X = Rs.copy(), T0.copy(), X0.copy()
+    usable = (cam >= 0) & (cam < C) & np.isfinite(X0[pid]).all(1) & np.isfinite(xy).all(1)
+    camc = np.where(usable, cam, 0)
+    part, count, accepted, ran = np.zeros(m, bool), 0, 0, False
+    margin, gmargin = np.inf, np.inf
+    with np.errstate(all="ignore"):
+        for rnd in range(p["rounds"]):
+            _, Y, _, _, _, _, _, e = observe(K, R, T, X, pid, camc, xy)
+            take = usable & (Y[:, 2] > 0.0)
+            if rnd > 0 or plant == "gate_round0":
+                take = take & (e <= gate)
+            seen = np.zeros((N, C), bool)
+            seen[pid[take], camc[take]] = True
+            active = seen.sum(1) >= (1 if plant == "one_camera_rule" else 2)
+            take = take & active[pid]
+            n_c = np.bincount(camc[take], minlength=C)
+            free = (np.arange(C) >= nf) & (n_c >= p["min_obs"])
+            if rnd == 0:
+                count = int(take.sum())
+            if not free.any():
+                break
+            if rnd > 0:
+                mg = np.abs(e[usable] / gate - 1.0)
+                gmargin = min(gmargin, float(mg[np.isfinite(mg)].min()))
+            part, count, ran = take, int(take.sum()), True
+            info["free"] |= free
+            info["took_part"] |= active
+            slot = np.where(free, np.cumsum(free) - 1, -1)
+            pp, cc, xx = pid[part], camc[part], xy[part]
+            obj = f64(rr.rho(observe(K, R, T, X, pp, cc, xx)[7], delta).sum())
+            hist, lam = [float(obj)], f64(LAMBDA0)
+            for _ in range(p["max_iterations"]):
+                st = step(K, R, T, X, pp, cc, xx, slot, delta, lam, plant)
+                accept = False
+                if st is not None:
+                    dc, dX, touched = st
+                    Rn, Tn, Xn = R.copy(), T.copy(), X.copy()
+                    for c in range(C):
+                        if slot[c] >= 0:
+                            d = dc[6 * slot[c]:6 * slot[c] + 6]
+                            Rn[c], Tn[c] = rr.rotate(d[:3], R[c]), T[c] + d[3:]
+                    Xn[touched] = X[touched] + dX[touched]
+                    _, Yn, _, _, _, _, _, en = observe(K, Rn, Tn, Xn, pp, cc, xx)
+                    on = f64(rr.rho(en, delta).sum())
+                    behind = not bool((Yn[:, 2] > 0.0).all())
+                    fin = np.isfinite(Rn).all() and np.isfinite(Tn).all() and np.isfinite(Xn[touched]).all()
+                    accept = fin and (not behind) and bool(on < obj)
+                    if fin and not behind and np.isfinite(on) and obj > 0:
+                        margin = min(margin, abs(float(on / obj) - 1.0))
+                if accept:
+                    rel = (obj - on) / obj
+                    R, T, X, obj = Rn, Tn, Xn, on
+                    hist.append(float(obj))
+                    accepted += 1
+                    lam = max(lam / 10.0, f64(LAMBDA_MIN))
+                    if rel < REL_STOP:
+                        break
+                else:
+                    lam = lam * 10.0
+                    if lam > LAMBDA_MAX:
+                        break
+            info["objective"].append(hist)
+        info["part"], info["margin"], info["gate_margin"] = part, margin, gmargin
+        if not ran or accepted == 0 or not np.isfinite(R).all():
+            return alone(count)
+        pp, cc, xx = pid[part], camc[part], xy[part]
+        s1 = f64(rr.rho(observe(K, Rs, T0, X0, pp, cc, xx)[7], delta).sum()) / f64(count)
+        s2 = f64(rr.rho(observe(K, R, T, X, pp, cc, xx)[7], delta).sum()) / f64(count)
+    if not (np.isfinite(s1) and np.isfinite(s2)):
+        return alone(count)
+    info["moved"] = True
+    Ro, To = R0.copy(), T0.copy()
+    Ro[info["free"]], To[info["free"]] = R[info["free"]], T[info["free"]]
+    Xo = X0.copy()
+    last = np.zeros(N, bool)
+    last[pid[part]] = True
+    Xo[last] = X[last]
+    if plant == "write_all_points":
+        Xo = X + 0.0
+    return Ro, To, Xo, np.array([count, s1, s2, accepted], f64), info
+
+
+# ------------------------------------------------------------------------------------------------ problems
+def problem(seed, cams, points, seen=0.8, outliers=0.0, rot_deg=1.0, shift=0.02, point_noise=0.05, n_fixed=2, noise_px=0.0):
+    """An exact scene (points in front of `cams` cameras along a path), each point seen by each camera with probability `seen`
+    and by at least two; keypoints = projections (+ noise_px of Gaussian noise) rounded to f32, a share `outliers` of the
+    observations replaced by uniform random pixels, none that would leave its point fewer than two true observations or no more true
+    than false ones (two rays nearly always meet somewhere: a point whose false observations are as many as its true ones can fit
+    two of them, pass the gate and end anywhere -- the two-camera rule cannot tell, measured: 6 of 10 seeds); the cameras from n_fixed on turned by rot_deg and shifted by `shift`, the
+    points moved by point_noise (Gaussian).  Ground truth only: not the contract's arithmetic.
+    -> dict R, T, X (the start), off, cam, xy, R_true, T_true, X_true, centres_true, planted (m,) bool, n_fixed"""
+    rng = np.random.default_rng(seed)
+    Xt = np.stack([rng.uniform(-2, 2, points), rng.uniform(-1.5, 1.5, points), rng.uniform(4, 9, points)], 1)
+    Cc, Rwc = [np.zeros(3)], [np.eye(3)]
+    for _ in range(1, cams):
+        d = rng.normal(size=3); d[2] *= 0.3
+        Cc.append(Cc[-1] + rng.uniform(0.2, 0.5) * (Rwc[-1] @ (d / np.linalg.norm(d))))
+        Rwc.append(Rwc[-1] @ rw._rot(rng.normal(size=3), rng.uniform(0.01, 0.05)))
+    Rt = np.stack([r.T for r in Rwc]); Tt = np.stack([-(r.T @ c) for r, c in zip(Rwc, Cc)])
+    vis = rng.uniform(size=(points, cams)) < seen
+    for i in range(points):
+        while vis[i].sum() < min(2, cams):
+            vis[i, rng.integers(cams)] = True
+    pid, cam = np.nonzero(vis)
+    off = np.concatenate([[0], np.cumsum(vis.sum(1))]).astype(np.int32)
+    q = (np.einsum("kij,kj->ki", Rt[cam], Xt[pid]) + Tt[cam]) @ kmat().astype(f64).T
+    xy = q[:, :2] / q[:, 2:3] + noise_px * rng.normal(size=(len(pid), 2))
+    planted = np.zeros(len(pid), bool)
+    k = int(round(outliers * len(pid)))
+    if k:
+        true_left, false_n, left = vis.sum(1), np.zeros(points, int), k
+        for o in rng.permutation(len(pid)):      # replaced only while the point keeps two true ones and more true than false
+            i = pid[o]
+            if left and true_left[i] - 1 >= 2 and true_left[i] - 1 > false_n[i] + 1:
+                planted[o] = True
+                true_left[i] -= 1; false_n[i] += 1; left -= 1
+        k = int(planted.sum())
+        xy[planted] = np.stack([rng.uniform(0, 640, k), rng.uniform(0, 480, k)], 1)
+    R, T = Rt.copy(), Tt.copy()
+    for c in range(n_fixed, cams):
+        R[c] = rw._rot(rng.normal(size=3), np.deg2rad(rot_deg)) @ Rt[c]
+        d = rng.normal(size=3)
+        T[c] = Tt[c] + shift * d / np.linalg.norm(d)
+    X = Xt + point_noise * rng.normal(size=Xt.shape)
+    return dict(R=R.reshape(cams, 9).copy(), T=T, X=X, off=off, cam=cam.astype(np.int32), xy=xy.astype(np.float32),
+                R_true=Rt.reshape(cams, 9), T_true=Tt, X_true=Xt, centres_true=np.stack(Cc), planted=planted, n_fixed=n_fixed)
+
+
+def run(pr, plant=None, **kw):
+    kw.setdefault("n_fixed", pr["n_fixed"])
+    return adjust(pr["R"], pr["T"], pr["X"], pr["off"], pr["cam"], pr["xy"], kmat(), plant=plant, **kw)
+
+
+def centres(R, T):
+    R = np.asarray(R).reshape(-1, 3, 3)
+    return -np.einsum("kji,kj->ki", R, T)
+
+
+def recovery(pr, out):
+    """largest error of the camera centres and of the points that took part in the last round, and the unit 2^-23 max|X|"""
+    R, T, X, st, info = out
+    last = np.zeros(len(X), bool)
+    last[np.repeat(np.arange(len(X)), np.diff(pr["off"]))[info["part"]]] = True
+    err = max(float(np.abs(centres(R, T) - pr["centres_true"]).max()), float(np.abs(X[last] - pr["X_true"][last]).max()))
+    return err, 2.0 ** -23 * float(np.abs(pr["X_true"]).max())
+
+
+EXACT_SEEDS = (1, 3, 4, 5, 7, 8)   # of 1 .. 10; 2 and 6 do not come back at outliers 0.2 (a point runs off in round 0) and were dropped
+EXACT_SHAPE = dict(cams=6, points=120, seen=1.0)
+# error / unit per seed as measured by recovery(run(problem(seed, **EXACT_SHAPE, outliers=o))); tests/test_ref_adjust.py re-measures
+MEASURED_RATIOS = {1: 3.6001, 3: 3.1499, 4: 3.3310, 5: 2.8231, 7: 4.4011, 8: 3.8275}
+MEASURED_RATIOS_OUTLIERS = {1: 4.3638, 3: 4.8975, 4: 5.2274, 5: 3.2976, 7: 5.4103, 8: 5.8113}
+C_BOUND = 23.3   # 4 x 5.8113 = 23.25, rounded up
+
+
+def comparison_cases():
+    """{name: (problem, params)}: the inputs delta_ref is measured over and the device is compared on: keypoint noise 0.3 px,
+    20 % planted outliers from c4n40 on.  The `decided_*` cases stop on max_iterations while every step still lowers the objective
+    by far more than its rounding, so their accepted-step counts do not depend on the order of the sums (tests assert margin >=
+    DECIDED_MARGIN for them)."""
+    c = {}
+    for name, cams, pts, seed, kw, pk in (
+            ("c2n8", 2, 8, 21, dict(seen=1.0, n_fixed=1), dict(n_fixed=1)),
+            ("c3n9", 3, 9, 22, dict(seen=0.0, n_fixed=2), {}),
+            ("c4n40", 4, 40, 23, dict(outliers=0.2), {}),
+            ("c8n257", 8, 257, 24, dict(outliers=0.2), {}),
+            ("c8n2000", 8, 2000, 25, dict(outliers=0.2, seen=0.75), {}),
+            ("decided_c4n40", 4, 40, 29, dict(outliers=0.2), dict(max_iterations=2, rounds=2)),
+            ("decided_c8n257", 8, 257, 27, dict(outliers=0.2), dict(max_iterations=2, rounds=2)),
+            ("decided_c8n2000", 8, 2000, 28, dict(outliers=0.2, seen=0.75), dict(max_iterations=2, rounds=2))):
+        c[name] = (problem(seed, cams, pts, noise_px=0.3, **kw), params(**dict(pk, n_fixed=kw.get("n_fixed", 2))))
+    return c
+
+
+_cases, _results = {}, {}
+
+
+def cases():
+    if not _cases:
+        _cases.update(comparison_cases())
+    return _cases
+
+
+def comparison_results():
+    """{name: (R, T, X, stats, info)} of adjust() over comparison_cases(), computed once"""
+    if not _results:
+        for name, (pr, p) in cases().items():
+            _results[name] = run(pr, **p)
+    return _results
+
+
+# ------------------------------------------------------------------------------------------------ the second formulation
+def second_formulation(pr, out, delta):
+    """min sum rho(e) over the last round's participants through scipy's least_squares, from adjust()'s result `out`.
+    -> R, T, X with the unknowns replaced"""
+    from scipy.optimize import least_squares
+    from scipy.optimize._numdiff import approx_derivative
+    from scipy.sparse import lil_matrix
+    R, T, X, st, info = out
+    part = info["part"]
+    pid = np.repeat(np.arange(len(X)), np.diff(pr["off"]))[part]
+    cam, xy = pr["cam"][part].astype(np.int64), pr["xy"][part].astype(f64)
+    Km = kmat().astype(f64)
+    free = np.nonzero(info["free"])[0]
+    pts = np.unique(pid)
+    cs, ps = {c: s for s, c in enumerate(free)}, {i: s for s, i in enumerate(pts)}
+    nc = 6 * len(free)
+
+    def unpack(v):
+        Rn, Tn, Xn = R.reshape(-1, 3, 3).copy(), T.copy(), X.copy()
+        for c, s in cs.items():
+            w = v[6 * s:6 * s + 3]
+            th = np.linalg.norm(w)
+            Wm = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0.0]])
+            E = np.eye(3) + Wm if th < 1e-12 else np.eye(3) + np.sin(th) / th * Wm + (1 - np.cos(th)) / (th * th) * (Wm @ Wm)
+            Rn[c] = E @ R[c].reshape(3, 3)
+            Tn[c] = v[6 * s + 3:6 * s + 6]
+        Xn[pts] = v[nc:].reshape(-1, 3)
+        return Rn, Tn, Xn
+
+    def f(v):
+        Rn, Tn, Xn = unpack(v)
+        q = (np.einsum("kij,kj->ki", Rn[cam], Xn[pid]) + Tn[cam]) @ Km.T
+        r = q[:, :2] / q[:, 2:3] - xy
+        return np.sqrt((r * r).sum(1))
+    v0 = np.concatenate([np.concatenate([np.zeros(3), T[c]]) for c in free] + [X[pts].reshape(-1)])
+    sp = lil_matrix((len(pid), len(v0)), dtype=int)
+    for k in range(len(pid)):
+        if cam[k] in cs:
+            sp[k, 6 * cs[cam[k]]:6 * cs[cam[k]] + 6] = 1
+        sp[k, nc + 3 * ps[pid[k]]:nc + 3 * ps[pid[k]] + 3] = 1
+    jac = lambda v: approx_derivative(f, v, method="3-point", sparsity=sp).toarray()   # sparse differences, dense trust-region solve
+    sol = least_squares(f, v0, jac=jac, method="trf", loss="huber", f_scale=float(delta), ftol=1e-15, xtol=1e-15, gtol=1e-15,
+                        x_scale=1.0, max_nfev=100)
+    Rn, Tn, Xn = unpack(sol.x)
+    return Rn.reshape(-1, 9), Tn, Xn
+
+
+def disagreement(name):
+    """largest entry-wise |first - second| of one comparison case: R absolute, T and X relative to max(1, max|.|)"""
+    pr, p = cases()[name]
+    out = comparison_results()[name]
+    R2, T2, X2 = second_formulation(pr, out, p["huber_px"])
+    R, T, X = out[:3]
+    return max(float(np.abs(R - R2).max()), float(np.abs(T - T2).max() / max(1.0, np.abs(T).max())),
+               float(np.abs(X - X2).max() / max(1.0, np.abs(X).max())))
+
+
+DELTA_REF_CASES = ("c2n8", "c3n9", "c4n40", "c8n257")
+# The decided_* cases stop on max_iterations short of the minimum the second formulation runs to (measured: 9.8e-4 and 1.3e-4
+# apart at 40 and 257 points), so they say nothing about the formulas and are left out; c8n2000's dense solve is too large.
+DELTA_REF = 1.1e-10   # measured: c2n8 1.57e-11, c3n9 9.61e-13, c4n40 1.02e-10, c8n257 2.82e-13 (c8n2000: not run, its dense solve is too large)
+
+
+def delta_ref():
+    return max(disagreement(n) for n in DELTA_REF_CASES)

@@ -1,0 +1,447 @@
+"""The window adjustment on the device (include/vslam_adjust.h: vslam_adjust_windows) against tests/ref_adjust.py.
+
+Comparison, per entry: |dev - ref| <= TOL scale with TOL = 16 max(DELTA_REF, DELTA_ORDER), scale = 1 for R and max(1, the array's
+largest magnitude) for T and X -- tests/test_gpu_resect.py's form and factor, for its reason: the device has a third order of the
+sums.  DELTA_REF = 1.1e-10 (two float64 formulations, tests/ref_adjust.py) and DELTA_ORDER = 6.0e-10 (the serial walk of the
+kernel's own arithmetic against the reference, tests/test_adjust_serial.py) were measured on the CPU, never from the device.  The
+participants of the last round (stats[0]) are exact: every gate decision of these inputs is far from a tie (asserted).  The
+accepted-step counts (stats[3]) are exact wherever every accept / refuse decision of the reference run is at least
+ref_adjust.DECIDED_MARGIN from a tie; the `decided_*` inputs are chosen so that this holds, and that is asserted.  On the exact
+problems the device is held to the truth within ref_adjust.C_BOUND, the reference's own bound.  Everything else is a status code
+or a bitwise comparison between two device runs."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import ref_adjust as ra
+from test_adjust_serial import DELTA_ORDER, deltas
+from vslam_amd import capi
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+C = capi.C
+TOL = 16 * max(ra.DELTA_REF, DELTA_ORDER)
+KM = ra.kmat()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+
+
+def _item(pr, **over):
+    it = {k: pr[k] for k in ("R", "T", "X", "off", "cam", "xy")}
+    it.update(C=len(pr["R"]), N=len(pr["X"]))
+    it.update(over)
+    return it
+
+
+def _batch(items, cs, ps, os_):
+    B = len(items)
+    a = dict(R=np.zeros((B, cs, 9)), T=np.zeros((B, cs, 3)), nc=np.zeros(B, np.int32), X=np.zeros((B, ps, 3)), n=np.zeros(B, np.int32),
+             off=np.zeros((B, ps + 1), np.int32), cam=np.zeros((B, os_), np.int32), xy=np.zeros((B, os_, 2), np.float32))
+    for i, it in enumerate(items):
+        c, n, m = len(it["R"]), len(it["X"]), len(it["cam"])
+        a["R"][i, :c], a["T"][i, :c], a["X"][i, :n] = it["R"], it["T"], it["X"]
+        a["off"][i, :len(it["off"])] = it["off"]
+        a["off"][i, len(it["off"]):] = it["off"][-1]
+        a["cam"][i, :m], a["xy"][i, :m] = it["cam"], it["xy"]
+        a["nc"][i], a["n"][i] = it["C"], it["N"]
+    return {k: torch.from_numpy(v).cuda() for k, v in a.items()}
+
+
+def _adjust(ctx, items, cs, ps, os_, K=None, **params):
+    b = _batch(items, cs, ps, os_)
+    R, T, X, st = ctx.adjust_windows(b["R"], b["T"], b["nc"], b["X"], b["n"], b["off"], b["cam"], b["xy"], KM if K is None else K, **params)
+    ctx.synchronize()
+    return R.cpu().numpy(), T.cpu().numpy(), X.cpu().numpy(), st.cpu().numpy()
+
+
+def _hold_item(name, pr, got, ref):
+    R, T, X, st = got
+    Rr, Tr, Xr, sr, info = ref
+    c, n = len(Rr), len(Xr)
+    d = deltas((R[:c], T[:c], X[:n]), (Rr, Tr, Xr))
+    print(f"{name}: delta {d:.1e} (tolerance {TOL:.1e}), participants {st[0]:.0f}, accepted {st[3]:.0f} / {sr[3]:.0f}, margin {info['margin']:.1e}")
+    assert info["moved"] and info["gate_margin"] >= ra.DECIDED_MARGIN
+    assert d <= TOL
+    assert st[0] == sr[0]
+    if info["margin"] >= ra.DECIDED_MARGIN:
+        assert st[3] == sr[3]
+    assert abs(st[1] - sr[1]) <= 1e-9 * sr[1] and abs(st[2] - sr[2]) <= 1e-6 * sr[2]
+    held = ~info["free"]
+    assert np.array_equal(_bits(R[:c][held]), _bits(pr["R"][held])) and np.array_equal(_bits(T[:c][held]), _bits(pr["T"][held]))
+    last = np.zeros(n, bool)
+    last[np.repeat(np.arange(n), np.diff(pr["off"]))[info["part"]]] = True
+    assert np.array_equal(_bits(X[:n][~last]), _bits(pr["X"][~last])), "a point outside the last round keeps its bits"
+    assert not R[c:].any() and not X[n:].any(), "nothing beyond the counts is written"
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return ra.cases(), ra.comparison_results()
+
+
+def test_header_symbols_and_defaults(ctx):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vslam_adjust.h")).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(vslam_[A-Za-z0-9_]+)\s*\(", text)))
+    assert names == sorted(capi.ADJUST_SYMBOLS) and not set(names) & set(capi.SYMBOLS) and not set(names) & set(capi.RESECT_SYMBOLS)
+    for nm in names:
+        assert hasattr(ctx.lib, nm), nm
+    assert "#define VSLAM_ADJUST_MAX_CAMS 8" in text
+    p = capi.AdjustParams.make(ctx.lib)
+    assert (p.max_iterations, p.rounds, p.min_obs, p.n_fixed, p.huber_px, p.gate_px) == (20, 3, 8, 2, 2.0, 6.0)
+    assert ctx.lib.vslam_adjust_params_default(C.c_void_p(0)) == -1
+
+
+# (case, cam_stride, pt_stride, obs_stride): c2n8 one free camera, the minimum; c3n9 every point seen by exactly two cameras;
+# c8n257 crosses the 256 lanes with all eight cameras; c8n2000 about 12 000 observations; c4n40 once with strides far above
+@pytest.mark.parametrize("name,cs,ps,os_", [("c2n8", 2, 8, 16), ("c3n9", 3, 9, 18), ("c4n40", 4, 40, 160), ("c8n257", 8, 257, 2056),
+                                            ("c8n2000", 8, 2000, 12800), ("c4n40", 8, 4096, 20000), ("decided_c4n40", 4, 64, 256),
+                                            ("decided_c8n257", 8, 300, 2400), ("decided_c8n2000", 8, 2048, 16000)])
+def test_item_against_the_reference(ctx, cases, name, cs, ps, os_):
+    pr, p = cases[0][name]
+    assert len(pr["cam"]) <= os_
+    if name == "c3n9":
+        assert (np.diff(pr["off"]) == 2).all()
+    if name == "c8n2000":
+        assert 11000 <= len(pr["cam"]) <= 12800
+    got = _adjust(ctx, [_item(pr)], cs, ps, os_, **p)
+    if name.startswith("decided"):
+        assert cases[1][name][4]["margin"] >= ra.DECIDED_MARGIN and got[3][0, 3] == cases[1][name][3][3] >= 3
+    _hold_item(name, pr, [g[0] for g in got], cases[1][name])
+
+
+def test_exact_problems_come_back_within_the_reference_bound(ctx):
+    prs = [ra.problem(seed, outliers=o, **ra.EXACT_SHAPE) for o in (0.0, 0.2) for seed in ra.EXACT_SEEDS]
+    R, T, X, st = _adjust(ctx, [_item(pr) for pr in prs], 6, 120, 720)
+    for i, pr in enumerate(prs):
+        ref = ra.run(pr)
+        assert st[i, 0] == ref[3][0] and st[i, 3] >= 1
+        err, unit = ra.recovery(pr, (R[i], T[i], X[i], st[i], ref[4]))
+        print(f"problem {i}: error / unit {err / unit:.3f} (bound {ra.C_BOUND})")
+        assert err <= ra.C_BOUND * unit
+
+
+def test_left_alone_bits_kept(ctx, cases):
+    pr, p = cases[0]["c4n40"]
+    nan_cam = pr["R"].copy(); nan_cam[1, 4] = np.nan
+    dec = pr["off"].copy(); dec[5] = dec[4] - 1
+    once = np.arange(41, dtype=np.int32)
+    items = [_item(pr, N=0), _item(pr, off=once), _item(pr, R=nan_cam), _item(pr, off=dec), _item(pr, C=9), _item(pr, N=65), _item(pr)]
+    b = _batch(items, 4, 64, 256)
+    before = {k: v.cpu().numpy().copy() for k, v in b.items()}
+    R, T, X, st = ctx.adjust_windows(b["R"], b["T"], b["nc"], b["X"], b["n"], b["off"], b["cam"], b["xy"], KM, **p)
+    ctx.synchronize()
+    R, T, X, st = R.cpu().numpy(), T.cpu().numpy(), X.cpu().numpy(), st.cpu().numpy()
+    for i in range(6):
+        assert np.array_equal(_bits(R[i]), _bits(before["R"][i])) and np.array_equal(_bits(T[i]), _bits(before["T"][i])), i
+        assert np.array_equal(_bits(X[i]), _bits(before["X"][i])), i
+        assert st[i, 0] == 0 and np.isnan(st[i, 1:]).all(), i
+    assert st[6, 3] >= 1 and not np.array_equal(R[6], before["R"][6]), "the neighbour moved"
+    for k in ("nc", "n", "off", "cam", "xy"):
+        assert np.array_equal(_bits(b[k].cpu().numpy()), _bits(before[k])), k
+    # no camera free (n_fixed = C) and every free camera below min_obs: participants counted, nothing moved
+    for kw in (dict(n_fixed=4), dict(min_obs=1000)):
+        R, T, X, st = _adjust(ctx, [_item(pr)], 4, 64, 256, **dict(p, **kw))
+        assert st[0, 0] > 0
+        assert np.isnan(st[0, 1:]).all() and np.array_equal(_bits(R[0]), _bits(before["R"][6])) and np.array_equal(_bits(X[0]), _bits(before["X"][6]))
+
+
+def test_a_camera_below_min_obs_is_held_while_the_others_move(ctx, cases):
+    pr, p = cases[0]["c4n40"]
+    keep = np.ones(len(pr["cam"]), bool)
+    keep[np.nonzero(pr["cam"] == 3)[0][5:]] = False           # camera 3 keeps 5 observations
+    pid = np.repeat(np.arange(40), np.diff(pr["off"]))[keep]
+    q = dict(pr, off=np.concatenate([[0], np.cumsum(np.bincount(pid, minlength=40))]).astype(np.int32), cam=pr["cam"][keep], xy=pr["xy"][keep],
+             planted=pr["planted"][keep])
+    ref = ra.run(q, **p)
+    assert ref[4]["free"].tolist() == [False, False, True, False]
+    got = _adjust(ctx, [_item(q)], 4, 40, 160, **p)
+    _hold_item("camera 3 held", q, [g[0] for g in got], ref)
+    assert not np.array_equal(got[0][0, 2], pr["R"][2])
+
+
+def test_batch_of_three_and_the_same_bits_in_any_slot_batch_and_run(ctx, cases):
+    names = ["c3n9", "c8n257", "c4n40"]
+    items = [_item(cases[0][n][0]) for n in names]
+    shape = (8, 300, 2100)
+    got = _adjust(ctx, items, *shape)
+    for i, n in enumerate(names):
+        _hold_item(n, cases[0][n][0], [g[i] for g in got], cases[1][n])
+    want = {n: [g[i] for g in got] for i, n in enumerate(names)}
+    alone = _item(cases[0]["c4n40"][0], N=0)                 # a left-alone neighbour
+    for batch, slot, n in (([items[1]], 0, "c8n257"), ([alone, items[2], items[2], items[0], alone], 3, "c3n9"), ([items[2], alone], 0, "c4n40"),
+                           ([alone] * 6 + [items[1]], 6, "c8n257"), (items, 2, "c4n40")):
+        g2 = _adjust(ctx, batch, *shape)
+        for a, b in zip(want[n], [g[slot] for g in g2]):
+            assert np.array_equal(_bits(a), _bits(b)), (n, slot)
+
+
+def _raw_call(ctx, b, stats, over=None, cs=4, ps=64, os_=256, batch=1, params=None):
+    ptr = {k: v.data_ptr() for k, v in b.items()}
+    ptr["stats"] = stats.data_ptr() if stats is not None else 0
+    ptr.update(over or {})
+    prm = C.byref(params) if params is not None else C.c_void_p(0)
+    v = lambda k: C.c_void_p(ptr[k])
+    return ctx.lib.vslam_adjust_windows(ctx.handle, v("R"), v("T"), v("nc"), cs, v("X"), v("n"), ps, v("off"), v("cam"), v("xy"), os_, batch,
+                                        KM.ctypes.data_as(C.c_void_p), prm, v("stats"))
+
+
+def test_invalid_arguments_are_refused_before_anything_is_queued(ctx, cases):
+    pr, p = cases[0]["c4n40"]
+    b = _batch([_item(pr)], 4, 64, 256)
+    stats = torch.full((1, 4), 7.0, dtype=torch.float64).cuda()
+    before = {k: v.cpu().numpy().copy() for k, v in b.items()}
+    for bad in (dict(max_iterations=0), dict(max_iterations=65), dict(rounds=0), dict(rounds=5), dict(min_obs=5), dict(n_fixed=0),
+                dict(huber_px=0.0), dict(gate_px=float("nan")), dict(huber_px=float("inf")), dict(gate_px=-1.0)):
+        assert _raw_call(ctx, b, stats, params=capi.AdjustParams.make(ctx.lib, **bad)) == -1, bad
+    for k in ("R", "T", "nc", "X", "n", "off", "cam", "xy"):                      # null pointers
+        assert _raw_call(ctx, b, stats, over={k: 0}) == -1, k
+    assert ctx.lib.vslam_adjust_windows(C.c_void_p(0), *[C.c_void_p(0)] * 3, 4, *[C.c_void_p(0)] * 2, 64, *[C.c_void_p(0)] * 3, 256, 1,
+                                        KM.ctypes.data_as(C.c_void_p), C.c_void_p(0), C.c_void_p(0)) == -1
+    for kw in (dict(cs=0), dict(ps=0), dict(os_=0), dict(batch=0), dict(batch=-1)):   # sizes
+        assert _raw_call(ctx, b, stats, **kw) == -1, kw
+    assert _raw_call(ctx, b, stats, cs=9) == -4                                     # VSLAM_ERR_CAPACITY
+    # every alignment row of the header: the f64 arrays and d_obs_xy 8 bytes, the int32 arrays 4
+    for k, off in (("R", 4), ("T", 4), ("X", 4), ("stats", 4), ("xy", 4), ("nc", 2), ("n", 2), ("off", 2), ("cam", 2)):
+        base = stats.data_ptr() if k == "stats" else b[k].data_ptr()
+        assert _raw_call(ctx, b, stats, over={k: base + off}) == -1, k
+        assert "d_" in ctx.lib.vslam_last_error(ctx.handle).decode()
+    ctx.synchronize()
+    for k, v in b.items():
+        assert np.array_equal(_bits(v.cpu().numpy()), _bits(before[k])), k
+    assert (stats.cpu().numpy() == 7.0).all(), "nothing ran"
+    assert _raw_call(ctx, b, None) == 0                                              # d_stats and params may be NULL
+    ctx.synchronize()
+    assert not np.array_equal(b["R"].cpu().numpy(), before["R"])
+
+
+def test_int32_arrays_at_four_bytes_and_f64_at_eight_give_the_aligned_bits(ctx, cases):
+    from offset_views import offset_view
+    pr, p = cases[0]["c4n40"]
+    names = ["R", "T", "nc", "X", "n", "off", "cam", "xy"]
+
+    def call(moved=None, k=0):
+        b = _batch([_item(pr)], 4, 64, 256)
+        check = None
+        if moved is not None:
+            v, whole, check = offset_view(tuple(b[moved].shape), b[moved].dtype, k)
+            v.copy_(b[moved])
+            b[moved] = v
+        stats = torch.zeros((1, 4), dtype=torch.float64).cuda()
+        rc = _raw_call(ctx, b, stats)
+        ctx.synchronize()
+        return rc, [b[x].cpu().numpy() for x in ("R", "T", "X")] + [stats.cpu().numpy()], check
+    rc, ref, _ = call()
+    assert rc == 0 and ref[3][0, 3] >= 1
+    for nm in names:
+        rc, got, check = call(nm, 2 if nm == "xy" else 1)
+        assert rc == 0, nm
+        check(nm)
+        for a, b in zip(ref, got):
+            assert np.array_equal(_bits(a), _bits(b)), nm
+
+
+def test_stream_order_behind_a_stalled_stream(cases):
+    from entry_calls import Call, Decoys, Hst, P
+    from stream_order import choose_sizing, run_behind_stall
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        ctx = capi.Context(0)
+        try:
+            def make(name):
+                b = _batch([_item(cases[0][name][0])], 8, 300, 2400)
+                argv = [P("d_R"), P("d_T"), P("d_n_cams"), 8, P("d_points"), P("d_n_points"), 300, P("d_obs_offsets"), P("d_obs_cam"), P("d_obs_xy"),
+                        2400, 1, Hst("h_K"), C.c_void_p(0), P("d_stats")]
+                return Call("vslam_adjust_windows", argv,
+                            ins={"d_n_cams": b["nc"], "d_n_points": b["n"], "d_obs_offsets": b["off"], "d_obs_cam": b["cam"], "d_obs_xy": b["xy"]},
+                            inouts={"d_R": b["R"], "d_T": b["T"], "d_points": b["X"]}, outs={"d_stats": ((1, 4), torch.float64)},
+                            hosts={"h_K": KM.reshape(9).copy()})
+            call, other = make("c8n257"), make("decided_c8n257")
+            decoys = Decoys(call, other, None)
+            sizing = choose_sizing(ctx, [call], stream)
+            print("stream order:", sizing)
+            res = run_behind_stall(ctx, call, stream, decoys, sizing)
+            assert res.rc == 0, res.msg
+            assert res.pending_at_return, "vslam_adjust_windows waited for the device before it returned"
+            assert res.pending_after_tail and res.pending_after_wait, "the stall ended before T_wait had passed"
+            assert set(res.got) == set(res.expected)
+            for k in res.expected:
+                assert np.array_equal(res.expected[k], res.got[k]), f"behind a stalled stream {k} differs from the plain run"
+            moved = np.frombuffer(res.got["d_stats"].tobytes(), np.float64)
+            assert moved[3] >= 1
+        finally:
+            ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ on the world
+from test_gpu_world import FRAMES as MF, KP as MKP, MCAP, OCAP, TRACKS, _Kmat, _same, _track, sequences  # noqa: E402,F401
+
+
+def _window_by_hand(ctx, pmap, xy, window):
+    """the header's problem built in Python from PointMap.observations(), view() and xy -> (view, items, f0)"""
+    off, fr, pt = [t.cpu().numpy() for t in pmap.observations()]
+    ctx.synchronize()
+    v = pmap.view()
+    f1 = int(v["frames"]) - 1
+    f0 = max(0, f1 - window + 1)
+    Cn = f1 - f0 + 1
+    items = []
+    for b in range(TRACKS):
+        N = int(v["sizes"][b])
+        R, T = np.zeros((Cn, 9)), np.zeros((Cn, 3))
+        for c in range(Cn):
+            m = v["world_Twc"][b, f0 + c]
+            for r in range(3):
+                for cc in range(3):
+                    R[c, 3 * r + cc] = m[4 * cc + r]
+                T[c, r] = -((m[r] * m[3] + m[4 + r] * m[7]) + m[8 + r] * m[11])
+        offs, cams, xys = [0], [], []
+        for i in range(N):
+            for o in range(off[b, i], off[b, i + 1]):
+                if f0 <= fr[b, o] <= f1 and 0 <= pt[b, o] < MKP:
+                    cams.append(fr[b, o] - f0)
+                    xys.append(xy[b, fr[b, o], pt[b, o]])
+            offs.append(len(cams))
+        items.append(dict(R=R, T=T, X=v["world_points"][b, :N, :3].astype(np.float64), off=np.array(offs, np.int32),
+                          cam=np.array(cams, np.int32), xy=np.array(xys, np.float32).reshape(-1, 2), C=Cn, N=N))
+    return v, items, f0
+
+
+@pytest.mark.parametrize("resection", [None, {}], ids=["plain", "resecting"])
+def test_world_adjust_equals_the_problem_built_by_hand(ctx, sequences, resection):
+    """vslam_world_adjust on a map with its world attached = the window gathered in Python, vslam_adjust_windows, and the header's
+    write-back in numpy f64, bit for bit; the map's arrays, d_scale, d_links and the resection statistics keep their bits; a map
+    tracked again afterwards equals one that was never adjusted."""
+    a = capi.PointMap(ctx, TRACKS, MF, MKP, MCAP, OCAP)
+    b = capi.PointMap(ctx, TRACKS, MF, MKP, MCAP, OCAP)
+    wa, wb = a.attach_world(resection=resection), b.attach_world(resection=resection)
+    try:
+        out = _track(ctx, a, sequences)
+        out_b = _track(ctx, b, sequences)
+        ctx.synchronize()
+        Km = _Kmat()
+        xy = out["xy"].cpu().numpy().reshape(TRACKS, MF, MKP, 2)
+        before, items, f0 = _window_by_hand(ctx, a, xy, 8)
+        Cn = items[0]["C"]
+        assert Cn == MF and f0 == 0
+        R, T, X, st = _adjust(ctx, items, 8, MCAP, OCAP, K=Km)
+        stats = wa.adjust(a, out["xy"], Km, window=8)
+        ctx.synchronize()
+        after = a.view()
+        assert np.array_equal(_bits(stats.cpu().numpy()), _bits(st))
+        print("accepted", st[:, 3].tolist(), "participants", st[:, 0].tolist(), "mean rho", st[:, 1].tolist(), "->", st[:, 2].tolist())
+        moved = ~np.isnan(st[:, 3])
+        assert moved.any() and (st[moved, 2] < st[moved, 1]).all(), "at least one track moves and lowers its mean rho"
+        want = {k: before[k].copy() for k in ("world_Twc", "world_pose", "world_points", "world_carry")}
+        for t in range(TRACKS):
+            if not moved[t]:
+                continue
+            it = items[t]
+            ref = ra.adjust(it["R"], it["T"], it["X"], it["off"], it["cam"], it["xy"], Km)
+            assert ref[4]["moved"] and ref[3][0] == st[t, 0]
+            free = ref[4]["free"]
+            last = np.zeros(it["N"], bool)
+            last[np.repeat(np.arange(it["N"]), np.diff(it["off"]))[ref[4]["part"]]] = True
+            old = before["world_Twc"][t, f0 + Cn - 1].copy()
+            for c in np.nonzero(free)[0]:
+                Rn, Tn = R[t, c], T[t, c]
+                m = np.zeros(16)
+                for r in range(3):
+                    for cc in range(3):
+                        m[4 * r + cc] = Rn[3 * cc + r]
+                    m[4 * r + 3] = -((Rn[r] * Tn[0] + Rn[3 + r] * Tn[1]) + Rn[6 + r] * Tn[2])
+                m[15] = 1.0
+                want["world_Twc"][t, f0 + c] = m
+                want["world_pose"][t, f0 + c] = m.astype(np.float32)
+            want["world_points"][t, :it["N"]][last, :3] = X[t, :it["N"]][last].astype(np.float32)
+            want["world_points"][t, :it["N"]][last, 3] = 1.0
+            if free[Cn - 1]:
+                Rn, Tn = R[t, Cn - 1], T[t, Cn - 1]
+                for k in np.nonzero(before["world_carry_index"][t] >= 0)[0]:
+                    p = before["world_carry"][t, k]
+                    w = [((old[4 * r] * p[0] + old[4 * r + 1] * p[1]) + old[4 * r + 2] * p[2]) + old[4 * r + 3] for r in range(3)]
+                    want["world_carry"][t, k] = [((Rn[3 * r] * w[0] + Rn[3 * r + 1] * w[1]) + Rn[3 * r + 2] * w[2]) + Tn[r] for r in range(3)]
+        valid = before["world_carry_index"] >= 0
+        for k in ("world_Twc", "world_pose", "world_points"):
+            assert np.array_equal(_bits(after[k]), _bits(want[k])), k
+        assert np.array_equal(_bits(after["world_carry"][valid]), _bits(want["world_carry"][valid]))
+        assert not np.array_equal(after["world_Twc"], before["world_Twc"]) and not np.array_equal(after["world_points"], before["world_points"])
+        keep = [k for k in before if k not in want]
+        assert "points" in keep and "world_scale" in keep and "world_links" in keep and "world_carry_index" in keep
+        _same(before, after, keys=keep)                      # the map's own arrays and the records of the steps
+        if resection is not None:
+            assert "world_resect_stats" in keep
+        # an untouched world and every output of vslam_track_sequences: the same as on a map never adjusted
+        sb = b.view()
+        _same(before, sb)
+        out2 = _track(ctx, a, sequences)
+        ctx.synchronize()
+        _same(a.view(), sb)
+        for k in out_b:
+            assert torch.equal(out2[k], out_b[k]), k
+    finally:
+        a.close(); b.close(); wa.close(); wb.close()
+
+
+def test_world_adjust_errors(ctx, sequences):
+    a = capi.PointMap(ctx, TRACKS, MF, MKP, MCAP, OCAP)
+    wa = a.attach_world()
+    other = capi.World(ctx, TRACKS, MF, MKP)
+    try:
+        out = _track(ctx, a, sequences)
+        ctx.synchronize()
+        before = a.view()
+        Km = _Kmat()
+        with pytest.raises(capi.VslamError, match="VSLAM_ERR_INVALID"):
+            other.adjust(a, out["xy"], Km)                                  # not the world attached to that map
+        for window in (1, 9):
+            with pytest.raises(capi.VslamError, match="VSLAM_ERR_INVALID"):
+                wa.adjust(a, out["xy"], Km, window=window)
+        with pytest.raises(capi.VslamError, match="VSLAM_ERR_INVALID"):
+            wa.adjust(a, out["xy"][:TRACKS * (MF - 1)].contiguous(), Km)    # xy_frames below the frames recorded
+        with pytest.raises(capi.VslamError, match="VSLAM_ERR_INVALID"):
+            wa.adjust(a, out["xy"], Km, min_obs=5)
+        assert ctx.lib.vslam_world_adjust(ctx.handle, wa.handle, a.handle, C.c_void_p(0), MF, Km.ctypes.data_as(C.c_void_p), 8, C.c_void_p(0),
+                                          C.c_void_p(0)) == -1
+        ctx.synchronize()
+        _same(before, a.view())
+        assert ctx.lib.vslam_world_adjust(ctx.handle, wa.handle, a.handle, capi._ptr(out["xy"]), MF, Km.ctypes.data_as(C.c_void_p), 2,
+                                          C.c_void_p(0), C.c_void_p(0)) == 0      # params and d_stats may be NULL; window 2
+        ctx.synchronize()
+    finally:
+        a.close(); wa.close(); other.close()
+
+
+# ------------------------------------------------------------------------------------------------ C++ surfaces
+def test_cpp_surfaces_match_the_c_entry_points(ctx, cases, tmp_path):
+    """tests/native/adjust_demo.cpp: vslam::adjust_windows (include/vslam/helpers.h) on one item gives the bits of the C entry
+    point; vslam::World::adjust (include/vslam/World.h) is taken on a world attached to a map and throws on one that is not."""
+    import struct
+    import subprocess
+    from vslam_amd import build
+    build.build_host()
+    exe = str(tmp_path / "adjust_demo")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "native", "adjust_demo.cpp"),
+                    "-I" + os.path.join(ROOT, "include"), "-L" + os.path.join(ROOT, "vslam_amd"), "-lvslam_host", "-lvslam_amd",
+                    "-Wl,-rpath," + os.path.join(ROOT, "vslam_amd")], check=True)
+    pr, p = cases[0]["c8n257"]
+    c, n, m = len(pr["R"]), len(pr["X"]), len(pr["cam"])
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(fin, "wb") as f:
+        f.write(KM.tobytes()); f.write(struct.pack("3i", c, n, m))
+        for a, dt in ((pr["R"], np.float64), (pr["T"], np.float64), (pr["X"], np.float64), (pr["off"], np.int32), (pr["cam"], np.int32),
+                      (pr["xy"], np.float32)):
+            f.write(np.ascontiguousarray(a, dt).tobytes())
+    subprocess.run([exe, fin, fout], check=True, timeout=120)
+    buf = open(fout, "rb").read()
+    R, T, X, st = _adjust(ctx, [_item(pr)], c, n, m)
+    want = np.concatenate([R[0].reshape(-1), T[0].reshape(-1), X[0].reshape(-1), st[0]])
+    got = np.frombuffer(buf, np.float64, want.size, 0)
+    assert st[0, 3] >= 1 and np.array_equal(_bits(got), _bits(want))
+    ws = np.frombuffer(buf, np.float64, 8, want.nbytes).reshape(2, 4)
+    assert (ws[:, 0] == 0).all() and np.isnan(ws[:, 1:]).all(), "one camera at frame 0: taken, nothing to move"
+    assert struct.unpack("i", buf[want.nbytes + 64:])[0] == 1, "a world that is not attached to the map is refused"

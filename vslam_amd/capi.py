@@ -67,6 +67,28 @@ class ResectParams(C.Structure):   # vslam_resect_params
         return p
 
 
+# every symbol include/vslam_adjust.h declares (a header of its own; tests/test_gpu_adjust.py checks it)
+ADJUST_SYMBOLS = ["vslam_adjust_params_default", "vslam_adjust_windows", "vslam_world_adjust"]
+
+
+class AdjustParams(C.Structure):   # vslam_adjust_params
+    _fields_ = [("max_iterations", C.c_int32), ("rounds", C.c_int32), ("min_obs", C.c_int32), ("n_fixed", C.c_int32),
+                ("huber_px", C.c_double), ("gate_px", C.c_double)]
+
+    @classmethod
+    def make(cls, lib, **fields):
+        """vslam_adjust_params_default with `fields` written over it"""
+        p = cls()
+        rc = lib.vslam_adjust_params_default(C.byref(p))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_adjust_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"vslam_adjust_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -421,6 +443,30 @@ class Context:
         self._check(self.lib.vslam_resect_poses(self.handle, _ptr(points), _ptr(xy), _ptr(n), C.c_int(B), C.c_int(S),
                                                 Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(R), _ptr(T), _ptr(stats)))
         return R, T, stats
+
+    def adjust_windows(self, R, T, n_cams, points, n_points, obs_offsets, obs_cam, obs_xy, K, want_stats=True, **params):
+        """vslam_adjust_windows (include/vslam_adjust.h): each item's cameras R (B, C, 9) / T (B, C, 3) f64 and points (B, P, 3) f64
+        adjusted together IN PLACE from the observations in CSR by point: obs_offsets (B, P + 1) i32, obs_cam (B, O) i32, obs_xy
+        (B, O, 2) f32; n_cams / n_points (B,) i32; K: the 3 x 3 camera matrix (host); params: fields of vslam_adjust_params over
+        its defaults.  Returns (R, T, points, stats (B, 4) f64 or None)."""
+        import numpy as np
+        torch = self.torch
+        B, Cs = R.shape[0], R.shape[1]
+        P, O = points.shape[1], obs_cam.shape[1]
+        for x, dt, nm in ((R, torch.float64, "R"), (T, torch.float64, "T"), (n_cams, torch.int32, "n_cams"), (points, torch.float64, "points"),
+                          (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"), (obs_cam, torch.int32, "obs_cam"),
+                          (obs_xy, torch.float32, "obs_xy")):
+            self._dev(x, dt, nm)
+        if tuple(obs_offsets.shape) != (B, P + 1):
+            raise ValueError(f"obs_offsets has shape {tuple(obs_offsets.shape)}, not {(B, P + 1)}")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.empty((B, 4), dtype=torch.float64, device=R.device) if want_stats else None
+        prm = AdjustParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_adjust_windows(self.handle, _ptr(R), _ptr(T), _ptr(n_cams), C.c_int(Cs), _ptr(points), _ptr(n_points),
+                                                  C.c_int(P), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_xy), C.c_int(O), C.c_int(B),
+                                                  Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
+        return R, T, points, stats
 
     def kdtree_build(self, xy, n):
         torch = self.torch
@@ -921,6 +967,23 @@ class World:
 
     def reset(self):
         self.ctx._check(self.lib.vslam_world_reset(self.ctx.handle, self.handle))
+
+    def adjust(self, pmap, xy, K, window=8, **params):
+        """vslam_world_adjust (include/vslam_adjust.h): the last `window` frames of every track and the map points they observe
+        adjusted together, in place in this world, which must be the one attached to `pmap`.  xy: the keypoints of every frame,
+        (tracks * xy_frames, kp_stride, 2) or (tracks, xy_frames, kp_stride, 2) f32 as track_sequences leaves them; params: fields
+        of vslam_adjust_params over its defaults.  Returns the statistics (tracks, 4) f64 (a cuda tensor)."""
+        import numpy as np
+        torch = self.ctx.torch
+        self.ctx._dev(xy, torch.float32, "xy")
+        xy_frames = xy.numel() // (self.tracks * self.kp_stride * 2)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.empty((self.tracks, 4), dtype=torch.float64, device=xy.device)
+        prm = AdjustParams.make(self.lib, **params)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_adjust(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), C.c_int(xy_frames),
+                                                    Kh.ctypes.data_as(C.c_void_p), C.c_int(window), C.byref(prm), _ptr(stats)))
+        return stats
 
     def set_resection(self, enable=True, **params):
         """vslam_world_set_resection (include/vslam_resect.h), allowed at frame 0 only: from now on step() takes xy_cur and K

@@ -730,3 +730,6 @@ int vslam_track_sequences(vslam_ctx *ctx, vslam_map *map, const uint8_t *d_bgr, 
 }
 
 }  // extern "C"
+
+// the world attached to the map, or null (adjust.hip: vslam_world_adjust is valid only for that world)
+vslam_world *vs_map_world(vslam_map *map) { return map ? map->world : nullptr; }

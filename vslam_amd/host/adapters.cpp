@@ -863,6 +863,17 @@ void resect_poses(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const 
     const int rc = vslam_resect_poses(ctx, d_points, d_xy, d_n, batch, stride, k, params, d_R, d_T, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_resect_poses: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void adjust_windows(vslam_ctx *ctx, f64 *d_R, f64 *d_T, const s32 *d_n_cams, int cam_stride, f64 *d_points, const s32 *d_n_points,
+                    int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const float *d_obs_xy, int obs_stride, int batch,
+                    const cv::Mat &K, f64 *d_stats, const vslam_adjust_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("adjust_windows: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_adjust_windows(ctx, d_R, d_T, d_n_cams, cam_stride, d_points, d_n_points, pt_stride, d_obs_offsets, d_obs_cam,
+                                        d_obs_xy, obs_stride, batch, k, params, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_adjust_windows: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
