@@ -7,8 +7,10 @@
 //   in.bin: int32 cam_stride, pt_stride, obs_stride, C, N, max_iterations, rounds, min_obs, n_fixed, 0; f64 huber, gate; K [9] f64;
 //           R [cam_stride][9], T [cam_stride][3], X [pt_stride][3] f64; int32 offsets [pt_stride + 1], cam [obs_stride];
 //           xy [obs_stride][2] f32
-//   stdout: moved (0 / 1); stats [4]; R; T; X -- %.17g, one line each
+//   stdout: moved (0 / 1); stats [4]; R; T; X -- %.17g, one line each; then the bits of X, one hexadecimal word per entry (a NaN's
+//           payload does not survive %.17g)
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <vector>
 
@@ -91,6 +93,12 @@ int main(int argc, char **argv) {
     for (double v : T) printf("%.17g ", v);
     printf("\n");
     for (double v : X) printf("%.17g ", v);
+    printf("\n");
+    for (double v : X) {
+        unsigned long long u;
+        memcpy(&u, &v, sizeof u);
+        printf("%llx ", u);
+    }
     printf("\n");
     return 0;
 }

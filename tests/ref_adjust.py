@@ -7,6 +7,10 @@ comparison's tolerance is for.
 
 adjust()                the adjustment of one item.
 problem()               synthetic items: an exact scene, keypoints rounded to f32, free cameras and points perturbed.
+ragged()                a generated item with one point of each kind the generator never makes (no observations, one camera only,
+                        a camera seen twice, cameras out of range, keypoints and a start that are not finite, a start behind).
+rule_cases()            the ragged items and the schedules where the free cameras change between rounds, seven and five slots,
+                        four rounds, one step; adjust() records the free cameras and the counts n_c of every round that ran.
 second_formulation()    the same objective over the last round's participants through scipy.optimize.least_squares(loss="huber",
                         f_scale=delta), one residual e = |r| per observation (scipy applies its loss per residual: with the norm as
                         the residual, rho(e) is exactly the header's), a rotation vector and T per free camera and every
@@ -218,7 +222,8 @@ def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
     """R_in (C, 9), T_in (C, 3), X_in (N, 3) f64; off (N + 1,), cam (m,) int; xy (m, 2) f32; K 3 x 3 f32.
     -> R, T, X, stats (4,), info.  Left alone: the inputs' bits.  info: moved, part (m,) bool (the last round's participants),
     free (C,) bool (free in some round), took_part (N,) bool (in some round; only the last round's points are written), margin (the closest accept / refuse decision to a
-    tie: |new / old - 1|), gate_margin (the closest gate decision: |e / gate - 1|), objective (accepted values per round)."""
+    tie: |new / old - 1|), gate_margin (the closest gate decision: |e / gate - 1|), objective (accepted values per round),
+    free_rounds / n_rounds (per round that ran: the free cameras (C,) bool and the counts n_c (C,))."""
     p = params(**kw)
     R0, T0, X0 = np.array(R_in, f64).reshape(-1, 9), np.array(T_in, f64).reshape(-1, 3), np.array(X_in, f64).reshape(-1, 3)
     off, cam = np.asarray(off, np.int64), np.asarray(cam, np.int64)
@@ -227,7 +232,7 @@ def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
     C, N = len(R0), len(X0)
     nan = float("nan")
     info = dict(moved=False, part=np.zeros(len(cam), bool), free=np.zeros(C, bool), took_part=np.zeros(N, bool), margin=np.inf,
-                gate_margin=np.inf, objective=[])
+                gate_margin=np.inf, objective=[], free_rounds=[], n_rounds=[])
 
     def alone(count):
         return R0.copy(), T0.copy(), X0.copy(), np.array([count, nan, nan, nan]), info
@@ -235,8 +240,8 @@ def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
         return alone(0)
     if not (np.isfinite(K).all() and np.isfinite(R0).all() and np.isfinite(T0).all()):
         return alone(0)
-    m = int(off[-1])
-    cam, xy = cam[:m], xy[:m]
+    m, o0 = int(off[-1]), int(off[0])
+    cam, xy = cam[o0:m], xy[o0:m]                # offsets[0] > 0: the observations in front belong to no point
     pid = np.repeat(np.arange(N), np.diff(off))
     delta, gate = f64(p["huber_px"]), f64(p["gate_px"])
     nf = 0 if plant == "fixed_moves" else p["n_fixed"]
@@ -270,6 +275,8 @@ def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
             part, count, ran = take, int(take.sum()), True
             info["free"] |= free
             info["took_part"] |= active
+            info["free_rounds"].append(free.copy())
+            info["n_rounds"].append(n_c.copy())
             slot = np.where(free, np.cumsum(free) - 1, -1)
             pp, cc, xx = pid[part], camc[part], xy[part]
             obj = f64(rr.rho(observe(K, R, T, X, pp, cc, xx)[7], delta).sum())
@@ -305,7 +312,7 @@ def adjust(R_in, T_in, X_in, off, cam, xy, K, plant=None, **kw):
                     if lam > LAMBDA_MAX:
                         break
             info["objective"].append(hist)
-        info["part"], info["margin"], info["gate_margin"] = part, margin, gmargin
+        info["part"], info["margin"], info["gate_margin"] = np.concatenate([np.zeros(o0, bool), part]), margin, gmargin
         if not ran or accepted == 0 or not np.isfinite(R).all():
             return alone(count)
         pp, cc, xx = pid[part], camc[part], xy[part]
@@ -432,6 +439,136 @@ def comparison_results():
         for name, (pr, p) in cases().items():
             _results[name] = run(pr, **p)
     return _results
+
+
+# ------------------------------------------------------------------------------------------------ the participation rules
+NAN_BITS = 0x7ff8000000000abc   # the quiet NaN (with a payload) that ragged() plants: its bits have to come back
+KINDS = ("empty", "same_cam_twice_only", "dup", "cam_range", "nan_xy", "inf_xy", "nan_X", "behind")
+
+
+def ragged(pr, seed):
+    """A generated problem with its CSR rebuilt so that one point of each kind of KINDS is in it -> (problem, kinds); kinds maps
+    each name to its point.  The points are taken in the order of a seeded permutation, each kind the next unused point that can
+    carry it: `dup`, `cam_range`, `nan_xy` and `inf_xy` need three true observations and no planted one (so that what is left of
+    the row still takes part), the others any point.
+      empty                 no observations
+      same_cam_twice_only   two observations, both by the camera of its first, 0.25 px apart: one camera, so it does not take part
+      dup                   a second observation by the camera of its last (a camera that is not held: pr["n_fixed"]), 0.25 px off,
+                            right behind it: the point takes part and the camera's blocks add
+      cam_range             an observation with camera C in front of its row and one with camera -1 behind it
+      nan_xy / inf_xy       the x of its first / the y of its last observation not finite
+      nan_X                 the start's x a NaN with a payload (NAN_BITS)
+      behind                the start at z = -3: out under the start
+    The result has the keys of problem() (planted rebuilt, the inserted observations not planted)."""
+    rng = np.random.default_rng(seed)
+    N, C = len(pr["X"]), len(pr["R"])
+    off = np.asarray(pr["off"], np.int64)
+    rows = [[(int(pr["cam"][k]), pr["xy"][k].copy(), bool(pr["planted"][k])) for k in range(off[i], off[i + 1])] for i in range(N)]
+    X = pr["X"].copy()
+    kinds, used = {}, set()
+    for kind in KINDS:
+        need = 3 if kind in ("dup", "cam_range", "nan_xy", "inf_xy") else 1
+        for i in rng.permutation(N):
+            if i not in used and len(rows[i]) >= need and (need == 1 or not any(o[2] for o in rows[i])) and (
+                    kind != "dup" or rows[i][-1][0] >= pr["n_fixed"]):
+                kinds[kind] = int(i)
+                used.add(int(i))
+                break
+        else:
+            raise ValueError("no point for " + kind)
+    shifted = lambda o: (o[0], o[1] + np.array([0.25, 0.0], np.float32), False)
+    i = kinds["empty"]; rows[i] = []
+    i = kinds["same_cam_twice_only"]; rows[i] = [rows[i][0], shifted(rows[i][0])]
+    i = kinds["dup"]; rows[i].append(shifted(rows[i][-1]))
+    i = kinds["cam_range"]; rows[i] = [(C, rows[i][0][1].copy(), False)] + rows[i] + [(-1, rows[i][-1][1].copy(), False)]
+    i = kinds["nan_xy"]; rows[i][0] = (rows[i][0][0], np.array([np.nan, rows[i][0][1][1]], np.float32), False)
+    i = kinds["inf_xy"]; rows[i][-1] = (rows[i][-1][0], np.array([rows[i][-1][1][0], np.inf], np.float32), False)
+    X[kinds["nan_X"], 0] = np.array([NAN_BITS], np.uint64).view(f64)[0]
+    X[kinds["behind"], 2] = -3.0
+    flat = [o for r in rows for o in r]
+    q = dict(pr, X=X, off=np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32),
+             cam=np.array([o[0] for o in flat], np.int32), xy=np.array([o[1] for o in flat], np.float32).reshape(-1, 2),
+             planted=np.array([o[2] for o in flat], bool))
+    return q, kinds
+
+
+def hold_kinds(pr, kinds, info):
+    """what ragged() is for, asserted on the reference's last round: who is in and who is out"""
+    off, part = pr["off"], info["part"]
+    row = lambda k: part[off[kinds[k]]:off[kinds[k] + 1]]
+    assert off[kinds["empty"] + 1] == off[kinds["empty"]]
+    for k in ("same_cam_twice_only", "nan_X", "behind"):
+        assert len(row(k)) >= 2 and not row(k).any(), k
+    i = kinds["dup"]
+    c = pr["cam"][off[i + 1] - 1]
+    assert c == pr["cam"][off[i + 1] - 2] and row("dup")[-2:].all() and row("dup").sum() >= 3, "both observations of the camera are in"
+    assert info["free_rounds"][-1][c], "and the camera is a slot of the last round: its blocks add"
+    r = row("cam_range")
+    assert not r[0] and not r[-1] and r[1:-1].all() and len(r) >= 5
+    r = row("nan_xy")
+    assert not r[0] and r[1:].all() and len(r) >= 3
+    r = row("inf_xy")
+    assert not r[-1] and r[:-1].all() and len(r) >= 3
+
+
+RAGGED_SEEDS = {"c4n40": 6, "c8n257": 1, "decided_c4n40": 3, "decided_c8n257": 3}
+# name -> (base case, parameters over the base's, n_fixed of a problem generated for the case or None, the free cameras per
+# round that ran -- the pattern the case is there for).  The min_obs values sit between the counts n_c of the rounds they
+# separate: the tests assert the pattern from info["free_rounds"] and the thresholds from info["n_rounds"].
+_RULES = {
+    "free_then_held_c4": ("decided_c4n40", dict(max_iterations=2, rounds=3, min_obs=26), None, ((2, 3), (2,), (2,))),
+    "no_free_round1_c4": ("decided_c4n40", dict(max_iterations=2, rounds=3, min_obs=29), None, ((2, 3),)),
+    "held_then_free_c8": ("decided_c8n257", dict(max_iterations=2, rounds=3, min_obs=152), None, ((2, 3, 4, 5, 6, 7), (2, 3, 4, 6, 7), (2, 3, 4, 5, 6, 7))),
+    "free_then_held_c8": ("decided_c8n257", dict(max_iterations=2, rounds=3, min_obs=153), None, ((2, 3, 4, 5, 6, 7), (2, 3, 4, 6, 7), (2, 3, 4, 6, 7))),
+    "no_free_round1_c8": ("decided_c8n257", dict(max_iterations=2, rounds=3, min_obs=176), None, ((2, 3, 4, 5, 6, 7),)),
+    "seven_slots": (None, dict(max_iterations=2, rounds=2), 1, ((1, 2, 3, 4, 5, 6, 7),) * 2),
+    "five_slots": (None, dict(max_iterations=2, rounds=2), 3, ((3, 4, 5, 6, 7),) * 2),
+    "rounds4": ("decided_c8n257", dict(max_iterations=2, rounds=4), None, ((2, 3, 4, 5, 6, 7),) * 4),
+    "one_step": ("decided_c8n257", dict(max_iterations=1, rounds=1), None, ((2, 3, 4, 5, 6, 7),)),
+}
+RULE_NO_FREE = ("no_free_round1_c4", "no_free_round1_c8")
+_rule_cases, _rule_kinds, _rule_results = {}, {}, {}
+
+
+def rule_cases():
+    """{name: (problem, params)}: inputs for the participation rules, the later-round rules, the slot counts and the schedules.
+    Not part of comparison_cases(): DELTA_REF / DELTA_ORDER are measured over those alone.  `ragged_*` also have
+    rule_kinds()[name]."""
+    if not _rule_cases:
+        base = cases()
+        for name, seed in RAGGED_SEEDS.items():
+            pr, p = base[name]
+            q, kinds = ragged(pr, seed)
+            _rule_cases["ragged_" + name] = (q, dict(p))
+            _rule_kinds["ragged_" + name] = kinds
+        for name, (src, pk, nf, _) in _RULES.items():
+            if src is None:
+                _rule_cases[name] = (problem(27, 8, 257, noise_px=0.3, outliers=0.2, n_fixed=nf), params(**dict(pk, n_fixed=nf)))
+            else:
+                _rule_cases[name] = (base[src][0], params(**dict(pk, n_fixed=base[src][1]["n_fixed"])))
+    return _rule_cases
+
+
+def rule_kinds():
+    rule_cases()
+    return _rule_kinds
+
+
+def rule_results():
+    """{name: (R, T, X, stats, info)} of adjust() over rule_cases(), computed once"""
+    if not _rule_results:
+        for name, (pr, p) in rule_cases().items():
+            _rule_results[name] = run(pr, **p)
+    return _rule_results
+
+
+def rule_pattern(name):
+    """the free cameras per round that ran which the case is there for"""
+    return _RULES[name][3] if name in _RULES else None
+
+
+def free_sets(info):
+    return tuple(tuple(int(c) for c in np.nonzero(f)[0]) for f in info["free_rounds"])
 
 
 # ------------------------------------------------------------------------------------------------ the second formulation
