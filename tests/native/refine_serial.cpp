@@ -1,10 +1,12 @@
-// The arithmetic of vslam_refine_pairs (vslam_amd/csrc/refine_math.h, the text the kernel compiles) on the host, one point after
-// the other: the iteration of include/vslam_amd.h with plain left-to-right sums where the device has its lane-strided ones.
-// tests/test_refine_serial.py holds its result to tests/ref_refine.py, which checks the formulas without a GPU.
+// The refinement of vslam_refine_pairs (vslam_amd/csrc/refine_math.h, the text the kernel compiles) on the host, one correspondence
+// after the other: ba_run with plain left-to-right sums where the device has its lane-strided ones.
+// tests/test_refine_serial.py holds its result to tests/ref_refine.py, which checks the formulas and the rules without a GPU.
 //
-// usage: refine_serial <in.bin> <max_iterations>      (build with -ffp-contract=off)
-//   in.bin: int32 n; K [9], R [9], t [3] f64 (the start: R, t as the device forms them); obs [n][4] f64; X [n][3] f64
-//   stdout: accepted steps, objective; R [9]; t [3]; X [n][3] -- %.17g
+// usage: refine_serial <in.bin>      (build with -ffp-contract=off; the test adds -fsanitize=address,undefined)
+//   in.bin: int32 n, winner, max_iterations, 0; f64 gate_sq; K [9], R [9], t [3] f64 (the f32 inputs widened); obs [n][4] f64;
+//           X [n][3] f64 (points4d widened)
+//   stdout: moved (0 / 1); stats [4]; accepted steps, objective; R [9]; t [3]; X of the participants [.][3] -- %.17g, the last
+//           four lines before the rounding to f32 (the inputs' R, t and no X when the pair is left alone)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -13,77 +15,61 @@
 
 using namespace vs_refine;
 
-int main(int argc, char **argv) {
-    if (argc < 3) return 2;
-    FILE *f = fopen(argv[1], "rb");
-    int n = 0;
-    if (!f || fread(&n, 4, 1, f) != 1 || n <= 0) return 3;
-    const int max_iterations = atoi(argv[2]);
-    std::vector<double> obs(4 * (size_t)n), X(3 * (size_t)n), Xn(3 * (size_t)n);
-    double K[9];
-    BaCam cur, cand;
-    if (fread(K, 8, 9, f) != 9 || fread(cur.R, 8, 9, f) != 9 || fread(cur.t, 8, 3, f) != 3 || fread(obs.data(), 8, 4 * (size_t)n, f) != 4 * (size_t)n ||
-        fread(X.data(), 8, 3 * (size_t)n, f) != 3 * (size_t)n)
-        return 3;
-    fclose(f);
-    auto point = [&](const std::vector<double> &P, int i, double (&x)[3], double (&o)[4]) {
-        for (int k = 0; k < 3; k++) x[k] = P[3 * (size_t)i + k];
+struct SerialEx {   // one caller owns every correspondence: its partial sums are the sums
+    int n;
+    const std::vector<double> &obs, &X;
+    std::vector<double> st;    // [2][3][n]
+    std::vector<uint8_t> fl;   // [n]
+    template <class F>
+    void each(int count, F f) const {
+        for (int i = 0; i < count; i++) f(i);
+    }
+    bool observed(int i, double (&o)[4]) const {
         for (int k = 0; k < 4; k++) o[k] = obs[4 * (size_t)i + k];
-    };
-    double obj = 0.0, lambda = kLambda0;
-    for (int i = 0; i < n; i++) {
-        double x[3], o[4], e1, e2, dz;
-        point(X, i, x, o);
-        ba_errors(K, cur, x, o, e1, e2, dz);
-        obj += e1 + e2;
+        return true;
     }
-    int accepted = 0;
-    for (int it = 0; it < max_iterations; it++) {
-        double b1[3], b2[3], acc[20] = {0}, dc[5];
-        ba_tangent(cur.t, b1, b2);
-        bool bad = false;
-        for (int i = 0; i < n; i++) {
-            double x[3], o[4], Yv[3][5], z[3], a[20];
-            point(X, i, x, o);
-            if (!ba_point_blocks(K, cur, b1, b2, lambda, x, o, Yv, z, a)) bad = true;
-            for (int k = 0; k < 20; k++) acc[k] += a[k];
-        }
-        bool accept = false;
-        double obj_new = 0.0;
-        if (!bad && ba_reduced_solve(acc, dc)) {
-            ba_candidate(cur, b1, b2, dc, cand);
-            bool behind = false;
-            for (int i = 0; i < n; i++) {
-                double x[3], o[4], Yv[3][5], z[3], a[20], xn[3], e1, e2, dz;
-                point(X, i, x, o);
-                ba_point_blocks(K, cur, b1, b2, lambda, x, o, Yv, z, a);
-                ba_point_step(x, Yv, z, dc, xn);
-                for (int k = 0; k < 3; k++) Xn[3 * (size_t)i + k] = xn[k];
-                ba_errors(K, cand, xn, o, e1, e2, dz);
-                obj_new += e1 + e2;
-                if (!(xn[2] > 0.0) || !(dz > 0.0)) behind = true;
-            }
-            accept = !behind && obj_new < obj;
-        }
-        if (accept) {
-            const double rel = (obj - obj_new) / obj;
-            cur = cand;
-            obj = obj_new;
-            X.swap(Xn);
-            accepted++;
-            lambda = fmax(lambda / 10.0, kLambdaMin);
-            if (rel < kRelStop) break;
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > kLambdaMax) break;
-        }
+    void input(int i, double (&x)[3]) const {
+        for (int k = 0; k < 3; k++) x[k] = X[3 * (size_t)i + k];
     }
-    printf("%d %.17g\n", accepted, obj);
-    for (int k = 0; k < 9; k++) printf("%.17g ", cur.R[k]);
+    double &state(int buf, int k, int i) { return st[((size_t)buf * 3 + k) * n + i]; }
+    uint8_t &flag(int i) { return fl[i]; }
+    template <int N>
+    void sum(double (&)[N]) {}
+    bool any(bool f) { return f; }
+};
+
+int main(int argc, char **argv) {
+    if (argc < 2) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    int hdr[4];
+    double gate_sq, K[9];
+    LmCam in;
+    if (!f || fread(hdr, 4, 4, f) != 4 || hdr[0] < 0 || fread(&gate_sq, 8, 1, f) != 1 || fread(K, 8, 9, f) != 9 ||
+        fread(in.R, 8, 9, f) != 9 || fread(in.T, 8, 3, f) != 3)
+        return 3;
+    const int n = hdr[0];
+    std::vector<double> obs(4 * (size_t)n), X(3 * (size_t)n);
+    if (fread(obs.data(), 8, obs.size(), f) != obs.size() || fread(X.data(), 8, X.size(), f) != X.size()) return 3;
+    fclose(f);
+    SerialEx ex{n, obs, X, std::vector<double>(6 * (size_t)n), std::vector<uint8_t>((size_t)n)};
+    BaResult res;
+    double stats[4];
+    const bool moved = ba_run(K, in, hdr[1], n, gate_sq, hdr[2], ex, res, stats);
+    if (!moved) {
+        res.cam = in;
+        res.objective = __builtin_nan("");
+    }
+    printf("%d\n", moved ? 1 : 0);
+    for (int k = 0; k < 4; k++) printf("%.17g ", stats[k]);
+    printf("\n%d %.17g\n", moved ? (int)stats[3] : 0, res.objective);
+    for (int k = 0; k < 9; k++) printf("%.17g ", res.cam.R[k]);
     printf("\n");
-    for (int k = 0; k < 3; k++) printf("%.17g ", cur.t[k]);
+    for (int k = 0; k < 3; k++) printf("%.17g ", res.cam.T[k]);
     printf("\n");
-    for (size_t k = 0; k < 3 * (size_t)n; k++) printf("%.17g ", X[k]);
+    for (int i = 0; moved && i < n; i++) {
+        if (!ex.fl[i]) continue;
+        for (int k = 0; k < 3; k++) printf("%.17g ", ex.state(res.buf, k, i));
+    }
     printf("\n");
     return 0;
 }

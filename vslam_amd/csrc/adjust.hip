@@ -3,12 +3,13 @@
 // rounds of adjust_math.h: lane l owns points l, l + 256, ... (their observations' blocks, the damped 3 x 3 solve, the point's
 // step), then the entries of the reduced system are dealt out over the lanes and each is summed over the points in ascending
 // order from what the points left in the arena -- a second pass by camera pair, no atomics --, the reduced system (at most
-// 42 x 42) is factored in the LDS with row i on lane i, and sums over the observations follow refit.hip's rule.  An item's bits
+// 42 x 42) is factored in the LDS with row i on lane i, and sums over the observations are block_reduce.h's.  An item's bits
 // depend on the item alone.
 #include <cmath>
 
 #include "ctx.h"
 #include "../../include/vslam_adjust.h"
+#include "block_reduce.h"
 #include "adjust_math.h"
 
 #pragma clang fp contract(off)
@@ -20,8 +21,7 @@ constexpr int kAT = 256;        // lanes per item
 constexpr int kAW = kAT / 64;   // waves per item
 constexpr int kASums = kAdMaxCams + 1;   // the widest sum: the counts per camera and their total
 
-struct BlockEx {
-    double *lds;   // [kAW][kASums]
+struct BlockEx : VsBlockReduce {   // lds: [kAW][kASums]
     template <class F>
     __device__ __forceinline__ void points(int n, F f) const {
         for (int i = threadIdx.x; i < n; i += kAT) f(i);
@@ -39,27 +39,6 @@ struct BlockEx {
         if (threadIdx.x == 0) f();
     }
     __device__ __forceinline__ void sync() const { __syncthreads(); }
-    template <int N>
-    __device__ __forceinline__ void sum(double (&v)[N]) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < N; i++) v[i] += __shfl_xor(v[i], off);
-        }
-        __syncthreads();   // the previous sum has been read by everyone
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < N; i++) lds[(threadIdx.x >> 6) * N + i] = v[i];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < N; i++) v[i] = ((lds[i] + lds[N + i]) + lds[2 * N + i]) + lds[3 * N + i];
-    }
-    __device__ __forceinline__ bool any(bool f) { return __syncthreads_or(f ? 1 : 0) != 0; }
-};
-
-struct AdK {
-    float v[9];
 };
 
 struct AdArgs {
@@ -76,7 +55,7 @@ struct AdArgs {
 };
 constexpr int kPerPoint = 9 + kAdMaxSlots * kAdStage;   // Xa, Xb, z, the staged blocks
 
-__global__ __launch_bounds__(kAT) void adjust_windows_kernel(AdArgs a, AdK Kc, AdParams prm) {
+__global__ __launch_bounds__(kAT) void adjust_windows_kernel(AdArgs a, VsK Kc, AdParams prm) {
     __shared__ AdShared sh;
     __shared__ double red[kAW * kASums];
     const int b = blockIdx.x;
@@ -101,7 +80,8 @@ __global__ __launch_bounds__(kAT) void adjust_windows_kernel(AdArgs a, AdK Kc, A
     w.mask = a.mask + (size_t)b * a.pt_stride;
     w.fa = a.flags + (size_t)b * 2 * a.obs_stride;
     w.fb = w.fa + a.obs_stride;
-    BlockEx ex{red};
+    BlockEx ex;
+    ex.lds = red;
     AdResult res;
     double stats[4];
     const bool moved = ad_run(K, it, prm, w, sh, ex, res, stats);   // the same in every lane
@@ -146,8 +126,7 @@ int launch_adjust(vslam_ctx *ctx, AdArgs a, int batch, const float *h_K, const v
     rc = vs_arena_get(ctx, "adjust_flags", (size_t)batch * 2 * a.obs_stride, &ptr);
     if (rc != VSLAM_OK) return rc;
     a.flags = static_cast<uint8_t *>(ptr);
-    AdK K;
-    for (int i = 0; i < 9; i++) K.v[i] = h_K[i];
+    const VsK K = vs_pack_K(h_K);
     AdParams q;
     q.max_iterations = p.max_iterations; q.rounds = p.rounds; q.min_obs = p.min_obs; q.n_fixed = p.n_fixed;
     q.huber = p.huber_px; q.gate = p.gate_px;

@@ -1,26 +1,17 @@
 // The arithmetic of the window adjustment (vslam_adjust_windows, include/vslam_adjust.h) that does not know about lanes: one
-// observation's blocks, a point's damped 3 x 3 solve, the entries of the reduced system, its Cholesky solve, the candidate, and
-// the rounds of the iteration written over one policy (Ex) that says who walks which points, entries and rows and how a sum over
-// the points is closed.  adjust.hip runs it with 256 lanes per item; tests/native/adjust_serial.cpp compiles the same text for the
-// host, walks everything one after the other and is held to tests/ref_adjust.py without a GPU.
-// All f64, never fused (compile host code with -ffp-contract=off).
+// observation's blocks, the entries of the reduced system, its Cholesky solve, and the rounds of the iteration written over one
+// policy (Ex) that says who walks which points, entries and rows and how a sum over the points is closed.  adjust.hip runs it
+// with 256 lanes per item; tests/native/adjust_serial.cpp compiles the same text for the host, walks everything one after the
+// other and is held to tests/ref_adjust.py without a GPU.  The camera, its start and candidate, the Jacobian's pieces and a
+// point's damped 3 x 3 solve are lm_math.h's.  All f64, never fused (compile host code with -ffp-contract=off).
 #pragma once
 
 #include <cstdint>
 
-#include "resect_math.h"
+#include "lm_math.h"
 
 namespace vs_adjust {
-using vs_refine::kDiagFloor;
-using vs_refine::kLambda0;
-using vs_refine::kLambdaMax;
-using vs_refine::kLambdaMin;
-using vs_refine::kRelStop;
-using vs_resect::RsCam;
-using vs_resect::RsPoint;
-using vs_resect::rs_point;
-using vs_resect::rs_rho;
-using vs_resect::rs_tri;
+using namespace vs_lm;
 
 constexpr int kAdMaxCams = 8;                 // VSLAM_ADJUST_MAX_CAMS
 constexpr int kAdMaxSlots = kAdMaxCams - 1;   // n_fixed >= 1
@@ -53,7 +44,7 @@ struct AdWork {   // per point and per observation, between the passes
 struct AdShared {   // one per item (LDS on the device)
     double S[kAdMaxN * kAdLd];   // lower triangle: S, then L below the diagonal
     double Ld[kAdMaxN], Ud[kAdMaxN], rhs[kAdMaxN], dc[kAdMaxN];
-    RsCam start[kAdMaxCams], cur[kAdMaxCams], cand[kAdMaxCams];
+    LmCam start[kAdMaxCams], cur[kAdMaxCams], cand[kAdMaxCams];
     int slot[kAdMaxCams];
     int flag;
 };
@@ -64,27 +55,24 @@ struct AdResult {
     int ever_free;     // bit c: camera c was free in some round
 };
 
-BA_FN double ad_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+LM_FN double ad_dot(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 // one observation's blocks at (c, X): V (upper 6: 00 01 02 11 12 22), gx, and -- for a free camera -- st[kAdW], st[kAdU], st[kAdG]
-BA_FN void ad_blocks(const double (&K)[9], const RsCam &c, double delta, const double (&X)[3], const double (&x)[2], bool free_cam,
+LM_FN void ad_blocks(const double (&K)[9], const LmCam &c, double delta, const double (&X)[3], const double (&x)[2], bool free_cam,
                      double (&V)[6], double (&gx)[3], double (&st)[kAdStage]) {
-    RsPoint o;
-    rs_point(K, c, X, x, o);
+    LmPoint o;
+    lm_point(K, c, X, x, o);
     double A[2][3], Jx[2][3], Jc[2][6];
-    vs_refine::ba_dproj(K, o.u, o.v, o.q2, A);
+    lm_dproj(K, o.u, o.v, o.q2, A);
+    lm_jac_point(A, c.R, Jx);
+    lm_jac_rotation(A, o.RX, Jc);
 #pragma unroll
     for (int r = 0; r < 2; r++) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) Jx[r][k] = (A[r][0] * c.R[k] + A[r][1] * c.R[3 + k]) + A[r][2] * c.R[6 + k];
-        Jc[r][0] = A[r][2] * o.RP[1] - A[r][1] * o.RP[2];
-        Jc[r][1] = A[r][0] * o.RP[2] - A[r][2] * o.RP[0];
-        Jc[r][2] = A[r][1] * o.RP[0] - A[r][0] * o.RP[1];
         Jc[r][3] = A[r][0];
         Jc[r][4] = A[r][1];
         Jc[r][5] = A[r][2];
     }
-    const double w = o.e <= delta ? 1.0 : delta / o.e;
+    const double w = lm_weight(o.e, delta);
     int t = 0;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -98,45 +86,14 @@ BA_FN void ad_blocks(const double (&K)[9], const RsCam &c, double delta, const d
 #pragma unroll
         for (int j = 0; j < 3; j++) st[kAdW + 3 * i + j] = w * (Jc[0][i] * Jx[0][j] + Jc[1][i] * Jx[1][j]);
 #pragma unroll
-        for (int j = i; j < 6; j++) st[kAdU + rs_tri(i, j)] = w * (Jc[0][i] * Jc[0][j] + Jc[1][i] * Jc[1][j]);
+        for (int j = i; j < 6; j++) st[kAdU + lm_tri<6>(i, j)] = w * (Jc[0][i] * Jc[0][j] + Jc[1][i] * Jc[1][j]);
         st[kAdG + i] = w * (Jc[0][i] * o.r[0] + Jc[1][i] * o.r[1]);
     }
 }
 
-struct AdChol3 {   // V* = L L^t
-    double l00, l10, l20, l11, l21, l22;
-    bool ok;
-    BA_FN void solve(const double *b, double *y) const {
-        const double f0 = b[0] / l00;
-        const double f1 = (b[1] - l10 * f0) / l11;
-        const double f2 = ((b[2] - l20 * f0) - l21 * f1) / l22;
-        y[2] = f2 / l22;
-        y[1] = (f1 - l21 * y[2]) / l11;
-        y[0] = ((f0 - l10 * y[1]) - l20 * y[2]) / l00;
-    }
-};
-
-BA_FN AdChol3 ad_chol3(const double (&V)[6], double lambda) {
-    AdChol3 c;
-    const double v00 = V[0] + lambda * fmax(V[0], kDiagFloor), v11 = V[3] + lambda * fmax(V[3], kDiagFloor),
-                 v22 = V[5] + lambda * fmax(V[5], kDiagFloor);
-    c.ok = v00 > 0.0;
-    c.l00 = sqrt(v00);
-    c.l10 = V[1] / c.l00;
-    c.l20 = V[2] / c.l00;
-    const double d1 = v11 - c.l10 * c.l10;
-    c.ok = c.ok && d1 > 0.0;
-    c.l11 = sqrt(d1);
-    c.l21 = (V[4] - c.l20 * c.l10) / c.l11;
-    const double d2 = (v22 - c.l20 * c.l20) - c.l21 * c.l21;
-    c.ok = c.ok && d2 > 0.0;
-    c.l22 = sqrt(d2);
-    return c;
-}
-
 // entry e of the reduced system over the points in ascending order: e < n is rhs[e]; the others walk the upper triangle row by
 // row, (I, J) with I <= J, stored at S[J][I]
-BA_FN void ad_entry(int e, int n, int N, const AdWork &w, AdShared &sh) {
+LM_FN void ad_entry(int e, int n, int N, const AdWork &w, AdShared &sh) {
     if (e < n) {
         const int a = e / 6, j = e % 6;
         double acc = 0.0;
@@ -156,7 +113,7 @@ BA_FN void ad_entry(int e, int n, int N, const AdWork &w, AdShared &sh) {
     const int J = I + t, a = I / 6, j = I % 6, b = J / 6, l = J % 6;
     double acc = 0.0, accu = 0.0;
     if (a == b) {
-        const int u = kAdU + rs_tri(j, l);
+        const int u = kAdU + lm_tri<6>(j, l);
         for (int i = 0; i < N; i++) {
             if (!((w.mask[i] >> a) & 1)) continue;
             const double *row = w.stage + ((size_t)i * kAdMaxSlots + a) * kAdStage;
@@ -177,7 +134,7 @@ BA_FN void ad_entry(int e, int n, int N, const AdWork &w, AdShared &sh) {
 }
 
 // row i's part of column j of the factor: the pivot p_j (every row forms it alike) and L_ij
-BA_FN void ad_chol_column(int i, int j, double lambda, AdShared &sh) {
+LM_FN void ad_chol_column(int i, int j, double lambda, AdShared &sh) {
     if (i < j) return;
     double p = sh.S[j * kAdLd + j] + lambda * fmax(sh.Ud[j], kDiagFloor);
     for (int k = 0; k < j; k++) p = p - sh.S[j * kAdLd + k] * sh.S[j * kAdLd + k];
@@ -192,7 +149,7 @@ BA_FN void ad_chol_column(int i, int j, double lambda, AdShared &sh) {
 }
 
 // L L^t d = rhs, dc = -d; raises the flag for a dc that is not finite
-BA_FN void ad_substitute(int n, AdShared &sh) {
+LM_FN void ad_substitute(int n, AdShared &sh) {
     double *f = sh.dc;
     for (int i = 0; i < n; i++) {
         double s = sh.rhs[i];
@@ -211,13 +168,13 @@ BA_FN void ad_substitute(int n, AdShared &sh) {
 }
 
 // whether point i has a participant among its observations
-BA_FN bool ad_took_part(const int32_t *off, const uint8_t *flags, int i) {
+LM_FN bool ad_took_part(const int32_t *off, const uint8_t *flags, int i) {
     bool any = false;
     for (int k = off[i]; k < off[i + 1]; k++) any = any || flags[k] != 0;
     return any;
 }
 
-BA_FN bool ad_finite3(const double (&v)[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+LM_FN bool ad_finite3(const double (&v)[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // The rounds of the adjustment.  Ex::points(N, f) calls f(i) for the points this caller owns (all of them on the host; l, l + 256,
 // ... for lane l), Ex::entries(n, f) and Ex::rows(n, f) likewise for the entries of the reduced system (strided) and for rows
@@ -225,7 +182,7 @@ BA_FN bool ad_finite3(const double (&v)[3]) { return std::isfinite(v[0]) && std:
 // everywhere afterwards; Ex::sync() makes what the callers wrote visible to one another.  Every decision is taken alike by every
 // caller.  Returns true with the cameras in sh.cur and the points in res.X when the item moved.
 template <class Ex>
-BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, const AdWork &w, AdShared &sh, Ex &ex, AdResult &res,
+LM_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, const AdWork &w, AdShared &sh, Ex &ex, AdResult &res,
                   double (&stats)[4]) {
     const double qnan = __builtin_nan("");
     stats[0] = 0.0;
@@ -240,14 +197,14 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
 #pragma unroll
     for (int k = 0; k < 9; k++) bad = bad || !std::isfinite(K[k]);
     ex.rows(C, [&](int c) {
-        RsCam in;
+        LmCam in;
 #pragma unroll
         for (int k = 0; k < 9; k++) in.R[k] = it.R[9 * c + k];
 #pragma unroll
         for (int k = 0; k < 3; k++) in.T[k] = it.T[3 * c + k];
-        bad = bad || !vs_resect::rs_finite(in);
-        RsCam st = in;
-        if (c >= p.n_fixed) vs_resect::rs_start(in, st);
+        bad = bad || !lm_finite(in);
+        LmCam st = in;
+        if (c >= p.n_fixed) lm_cam_start(in, st);
         sh.start[c] = st;
         sh.cur[c] = st;
     });
@@ -265,7 +222,7 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
     res.ever_free = 0;
 
     // sum of rho over the participants (flags fl) under (cams, Xp), and whether one of them is not in front of its camera
-    auto objective = [&](const RsCam *cams, const double *Xp, double &obj, bool &behind) {
+    auto objective = [&](const LmCam *cams, const double *Xp, double &obj, bool &behind) {
         double so[1] = {0.0};
         bool bh = false;
         ex.points(N, [&](int i) {
@@ -274,9 +231,9 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
                 if (!fl[k]) continue;
                 const float ox = it.xy[2 * (size_t)k], oy = it.xy[2 * (size_t)k + 1];
                 const double x[2] = {(double)ox, (double)oy};
-                RsPoint o;
-                rs_point(K, cams[it.cam[k]], X, x, o);
-                so[0] += rs_rho(o.e, p.huber);
+                LmPoint o;
+                lm_point(K, cams[it.cam[k]], X, x, o);
+                so[0] += lm_rho(o.e, p.huber);
                 bh = bh || !(o.Y[2] > 0.0);
             }
         });
@@ -300,8 +257,8 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
                 bool take = false;
                 if (xfin && c >= 0 && c < C && std::isfinite(ox) && std::isfinite(oy)) {
                     const double x[2] = {(double)ox, (double)oy};
-                    RsPoint o;
-                    rs_point(K, sh.cur[c], X, x, o);
+                    LmPoint o;
+                    lm_point(K, sh.cur[c], X, x, o);
                     take = o.Y[2] > 0.0 && (round == 0 || o.e <= p.gate);
                 }
                 fn[k] = take ? 1 : 0;
@@ -394,7 +351,7 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
                     w.mask[i] = 0;
                     return;
                 }
-                const AdChol3 ch = ad_chol3(V, lambda);
+                const LmChol3 ch = lm_chol3(V, lambda);
                 refuse = refuse || !ch.ok;
                 double z[3];
                 ch.solve(gx, z);
@@ -440,8 +397,8 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
                     double d[6];
 #pragma unroll
                     for (int q = 0; q < 6; q++) d[q] = sh.dc[6 * s + q];
-                    vs_resect::rs_candidate(sh.cur[c], d, sh.cand[c]);
-                    badx = badx || !vs_resect::rs_finite(sh.cand[c]);
+                    lm_cam_step(sh.cur[c], d, sh.cand[c]);
+                    badx = badx || !lm_finite(sh.cand[c]);
                 });
                 ex.points(N, [&](int i) {
                     const int m = w.mask[i];
@@ -495,7 +452,7 @@ BA_FN bool ad_run(const double (&K)[9], const AdItem &it, const AdParams &p, con
     }
     if (!ran || accepted == 0) return false;
     bool fin = true;
-    for (int c = 0; c < C; c++) fin = fin && vs_resect::rs_finite(sh.cur[c]);
+    for (int c = 0; c < C; c++) fin = fin && lm_finite(sh.cur[c]);
     double s0, s1;
     bool b0, b1;
     objective(sh.start, it.X, s0, b0);

@@ -155,6 +155,16 @@ struct VsStreamScope {
 
 static inline int vs_div_up(int a, int b) { return (a + b - 1) / b; }
 
+// the caller's camera matrix (h_K, row-major f32) as a kernel argument
+struct VsK {
+    float v[9];
+};
+static inline VsK vs_pack_K(const float *h_K) {
+    VsK K;
+    for (int i = 0; i < 9; i++) K.v[i] = h_K[i];
+    return K;
+}
+
 // Let `kernel` be launched with up to `bytes` of dynamic LDS; beyond the default limit a launch fails without this.  The
 // attribute is per device, so it is set once per context and remembered under `key`.  When a launch needs it (the limit
 // differs with the kernel's static LDS) is the caller's condition.

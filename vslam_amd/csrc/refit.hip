@@ -1,35 +1,15 @@
 // Refit of the RANSAC winner over its whole consensus set (vslam_refit_fundamental, include/vslam_amd.h): the step
 // find_fundamental leaves undone (src/RansacFilter.cpp:36-67 returns the winner as fitted to its 8 sampled, un-normalised
 // points; `//TODO: normalize` at :40).  One workgroup per pair, everything in f64, no floating-point atomics: every sum is a
-// per-lane strided partial sum, a butterfly inside the wave and the four wave sums left to right, so a pair's bits depend on
-// the pair alone -- not on the batch, the slot or the run.
+// per-lane strided partial sum closed by block_reduce.h, so a pair's bits depend on the pair alone -- not on the batch, the slot
+// or the run.
 #include "ctx.h"
+#include "block_reduce.h"
+#include "lm_math.h"
 
 namespace {
 constexpr int kRT = 256;        // lanes per pair
 constexpr int kRW = kRT / 64;   // waves per pair
-
-// Sum of v[i] over the workgroup, in every lane.  The butterfly adds the same two partial sums in both partners (a + b and
-// b + a: the same bits), so all lanes of a wave end with one value; the wave sums are added in wave order.
-template <int N>
-__device__ __forceinline__ void refit_block_sum(double (&v)[N], double *lds /* [kRW][N] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int i = 0; i < N; i++) v[i] += __shfl_xor(v[i], off);
-    }
-    __syncthreads();   // the previous sum has been read by everyone
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < N; i++) lds[(threadIdx.x >> 6) * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] = ((lds[i] + lds[N + i]) + lds[2 * N + i]) + lds[3 * N + i];
-}
-
-// index of (i, j), i <= j, among the 45 unique sums of the symmetric 9 x 9
-__host__ __device__ constexpr int refit_tri(int i, int j) { return i * 9 - i * (i - 1) / 2 + (j - i); }
 
 // e^2 / (Fx1_0^2 + Fx1_1^2 + Ftx2_0^2 + Ftx2_1^2), the true Sampson distance of one correspondence
 __device__ __forceinline__ double refit_sampson(const double (&F)[9], double u1, double v1, double u2, double v2) {
@@ -45,6 +25,7 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
                                                                 const float *F_in, float *F_out, double *__restrict__ stats) {
     __shared__ double red[kRW * 45];
     __shared__ double sM[81], sV[81];
+    const VsBlockReduce rd{red};
     const int b = blockIdx.x, tid = threadIdx.x;
     const float *p1 = xy1 + (size_t)b * kp_stride * 2, *p2 = xy2 + (size_t)b * kp_stride * 2;
     const int32_t *mt = matches + (size_t)b * kp_stride * 2;
@@ -76,7 +57,7 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
         if (!load(i, u1, v1, u2, v2)) continue;
         s5[0] += 1.0; s5[1] += u1; s5[2] += v1; s5[3] += u2; s5[4] += v2;
     }
-    refit_block_sum(s5, red);
+    rd.sum(s5);
     const double cnt = s5[0];
     const double cx1 = s5[1] / cnt, cy1 = s5[2] / cnt, cx2 = s5[3] / cnt, cy2 = s5[4] / cnt;
 
@@ -89,7 +70,7 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
         s2[0] += sqrt(dx1 * dx1 + dy1 * dy1);
         s2[1] += sqrt(dx2 * dx2 + dy2 * dy2);
     }
-    refit_block_sum(s2, red);
+    rd.sum(s2);
     const double d1 = s2[0] / cnt, d2 = s2[1] / cnt;
 
     const double qnan = __builtin_nan("");
@@ -120,10 +101,10 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
 #pragma unroll
         for (int p = 0; p < 9; p++) {
 #pragma unroll
-            for (int q = p; q < 9; q++) acc[refit_tri(p, q)] += r[p] * r[q];
+            for (int q = p; q < 9; q++) acc[vs_lm::lm_tri<9>(p, q)] += r[p] * r[q];
         }
     }
-    refit_block_sum(acc, red);
+    rd.sum(acc);
     // acc is indexed with constants only (it lives in registers): each lane picks its element through a chain of selects
     if (tid < 81) {
         const int i = tid / 9, j = tid % 9, lo = i < j ? i : j, hi = i < j ? j : i;
@@ -131,7 +112,7 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
 #pragma unroll
         for (int p = 0; p < 9; p++) {
 #pragma unroll
-            for (int q = p; q < 9; q++) m = (p == lo && q == hi) ? acc[refit_tri(p, q)] : m;
+            for (int q = p; q < 9; q++) m = (p == lo && q == hi) ? acc[vs_lm::lm_tri<9>(p, q)] : m;
         }
         sM[tid] = m;
         sV[tid] = i == j ? 1.0 : 0.0;
@@ -278,7 +259,7 @@ __global__ __launch_bounds__(kRT) void refit_fundamental_kernel(const float *__r
             ss[0] += refit_sampson(fin, u1, v1, u2, v2);
             ss[1] += refit_sampson(fout, u1, v1, u2, v2);
         }
-        refit_block_sum(ss, red);
+        rd.sum(ss);
     }
     if (tid == 0) {
 #pragma unroll

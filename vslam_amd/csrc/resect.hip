@@ -4,11 +4,11 @@
 // rounds of resect_math.h, and differ in where lane l finds its correspondences l, l + 256, ...: in the caller's arrays, or among
 // the step's matches (the links whose current keypoint is finite, with the OLD carry as the 3-D half).  Nothing is kept per
 // correspondence between two passes -- points and keypoints are read again, from L2 after the first pass -- so the LDS holds the
-// reduction's scratch and nothing else.  Sums follow refit.hip's rule (strided partial sums, a butterfly inside the wave, the
-// four wave sums in order), so an item's bits depend on the item alone.
+// reduction's scratch and nothing else.  Sums are block_reduce.h's, so an item's bits depend on the item alone.
 #include <cmath>
 
 #include "ctx.h"
+#include "block_reduce.h"
 #include "resect_math.h"
 #include "world_match.h"
 #include "world_select.h"
@@ -21,43 +21,6 @@ namespace {
 constexpr int kRT = 256;        // lanes per item
 constexpr int kRW = kRT / 64;   // waves per item
 constexpr int kRSums = 27;      // the widest sum: H (21) and g (6)
-
-struct BlockRed {
-    double *lds;   // [kRW][kRSums]
-    template <int N>
-    __device__ __forceinline__ void sum(double (&v)[N]) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < N; i++) v[i] += __shfl_xor(v[i], off);
-        }
-        __syncthreads();   // the previous sum has been read by everyone
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < N; i++) lds[(threadIdx.x >> 6) * N + i] = v[i];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < N; i++) v[i] = ((lds[i] + lds[N + i]) + lds[2 * N + i]) + lds[3 * N + i];
-    }
-    __device__ __forceinline__ bool any(bool f) { return __syncthreads_or(f ? 1 : 0) != 0; }
-};
-
-struct RsK {
-    float v[9];
-};
-
-struct RsP {   // vslam_resect_params as the kernels take it
-    int max_iterations, rounds, min_links;
-    double huber, gate;
-};
-
-__device__ __forceinline__ RsParams params_of(const RsP &p) {
-    RsParams q;
-    q.max_iterations = p.max_iterations; q.rounds = p.rounds; q.min_links = p.min_links;
-    q.huber = p.huber; q.gate = p.gate;
-    return q;
-}
 
 // the caller's arrays: correspondence i is (points[i], xy[i])
 struct ArraySrc {
@@ -101,12 +64,12 @@ struct LinkSrc {
 };
 
 __global__ __launch_bounds__(kRT) void resect_poses_kernel(const double *__restrict__ points, const float *__restrict__ xy,
-                                                           const int32_t *__restrict__ n_in, int stride, RsK Kc, RsP prm, double *R_io,
+                                                           const int32_t *__restrict__ n_in, int stride, VsK Kc, RsParams prm, double *R_io,
                                                            double *T_io, double *__restrict__ stats_out) {
     __shared__ double red[kRW * kRSums];
     const int b = blockIdx.x;
     double K[9];
-    RsCam in, out;
+    LmCam in, out;
 #pragma unroll
     for (int k = 0; k < 9; k++) {
         K[k] = (double)Kc.v[k];
@@ -118,9 +81,9 @@ __global__ __launch_bounds__(kRT) void resect_poses_kernel(const double *__restr
     src.P = points + (size_t)b * stride * 3;
     src.xy = reinterpret_cast<const float2 *>(xy) + (size_t)b * stride;
     src.n = min(max(n_in[b], 0), stride);
-    BlockRed rd{red};
+    VsBlockReduce rd{red};
     double stats[4];
-    const bool moved = rs_run(K, in, params_of(prm), src, rd, out, stats);
+    const bool moved = rs_run(K, in, prm, src, rd, out, stats);
     if (threadIdx.x != 0) return;
     if (moved) {
 #pragma unroll
@@ -151,7 +114,7 @@ __global__ __launch_bounds__(kRT) void world_resect_kernel(ResectWorld w, int fi
                                                            const int32_t *__restrict__ best, const float *__restrict__ points4d,
                                                            const float *__restrict__ Rf, const float *__restrict__ tf,
                                                            const int32_t *__restrict__ n_last, const int32_t *__restrict__ n_cur,
-                                                           const float *__restrict__ xy_cur, RsK Kc, RsP prm) {
+                                                           const float *__restrict__ xy_cur, VsK Kc, RsParams prm) {
     __shared__ double red[kRW * kRSums];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int K_ = w.kp_stride;
@@ -176,7 +139,7 @@ __global__ __launch_bounds__(kRT) void world_resect_kernel(ResectWorld w, int fi
     src.xy = reinterpret_cast<const float2 *>(xy_cur) + (size_t)b * K_;
     const double s0 = w.scale[fr];   // read by every lane before the first barrier, written behind the last one
     double K[9];
-    RsCam in, out;
+    LmCam in, out;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
         K[i] = (double)Kc.v[i];
@@ -188,9 +151,9 @@ __global__ __launch_bounds__(kRT) void world_resect_kernel(ResectWorld w, int fi
         src.t[i] = (double)tf[(size_t)b * 3 + i];
         in.T[i] = s0 * src.t[i];
     }
-    BlockRed rd{red};
+    VsBlockReduce rd{red};
     double stats[4];
-    const bool moved = rs_run(K, in, params_of(prm), src, rd, out, stats);   // the same in every lane
+    const bool moved = rs_run(K, in, prm, src, rd, out, stats);   // the same in every lane
     if (tid == 0) {
 #pragma unroll
         for (int k = 0; k < 4; k++) st[k] = stats[k];
@@ -233,8 +196,8 @@ __global__ __launch_bounds__(kRT) void world_resect_reset_kernel(double *stats, 
     if (i < count) stats[i] = (i & 3) == 0 ? 0.0 : __builtin_nan("");
 }
 
-RsP pack(const vslam_resect_params &p) {
-    RsP q;
+RsParams pack(const vslam_resect_params &p) {
+    RsParams q;
     q.max_iterations = p.max_iterations; q.rounds = p.rounds; q.min_links = p.min_links;
     q.huber = p.huber_px; q.gate = p.gate_px;
     return q;
@@ -262,8 +225,7 @@ int vs_launch_world_resect(vslam_ctx *ctx, vslam_world *w, int fid, const int32_
                            const float *R, const float *t, const int32_t *n_last, const int32_t *n_cur, const float *xy_cur,
                            const float *h_K) {
     VS_REQUIRE(ctx, xy_cur && h_K, VSLAM_ERR_INVALID);
-    RsK K;
-    for (int i = 0; i < 9; i++) K.v[i] = h_K[i];
+    const VsK K = vs_pack_K(h_K);
     ResectWorld d;
     d.max_frames = w->max_frames; d.kp_stride = w->kp_stride;
     d.Twc = w->Twc; d.pose = w->pose; d.scale = w->scale;
@@ -298,8 +260,7 @@ int vslam_resect_poses(vslam_ctx *ctx, const double *d_points, const float *d_xy
     vslam_resect_params_default(&p);
     if (params) p = *params;
     VS_REQUIRE(ctx, vs_resect_params_ok(p), VSLAM_ERR_INVALID);
-    RsK K;
-    for (int i = 0; i < 9; i++) K.v[i] = h_K[i];
+    const VsK K = vs_pack_K(h_K);
     VsProfScope ps(ctx, "resect_poses_kernel");
     resect_poses_kernel<<<batch, kRT, 0, ctx->stream>>>(d_points, d_xy, d_n, stride, K, pack(p), d_R, d_T, d_stats);
     VS_HIP(ctx, hipGetLastError());
