@@ -4,7 +4,7 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect] [--adjust]] [output directory]
+    python examples/render_map.py [--world [--resect] [--adjust] [--search]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
@@ -13,6 +13,9 @@ and on the right the same points and frusta in one coordinate system (vslam_worl
 chained from the pair's fundamental matrix alone; the accepted steps and participants per pair are printed.
 --adjust (with --world): after the last step the last window of 8 frames and the points they observe are adjusted together
 (World.adjust, include/vslam_adjust.h) and the world is drawn once more: track*_before_adjust.ppm / track*_after_adjust.ppm.
+--search (with --world): after the last step (and after --adjust) the last frame is searched by projection against the WHOLE map
+of its track and resected against what was found (World.search, include/vslam_search.h); found / seen per track are printed,
+beside the links the step itself had.
 """
 import os
 import sys
@@ -33,12 +36,13 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust", "--search")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
     adjust = "--adjust" in sys.argv[1:]
-    if (resect or adjust) and not with_world:
-        sys.exit("--resect and --adjust need --world")
+    search = "--search" in sys.argv[1:]
+    if (resect or adjust or search) and not with_world:
+        sys.exit("--resect, --adjust and --search need --world")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -104,6 +108,15 @@ def main():
                 write_ppm(os.path.join(out_dir, f"track{t}_before_adjust.ppm"), before[t])
                 write_ppm(os.path.join(out_dir, f"track{t}_after_adjust.ppm"), after[t])
             print("adjustment per track: participants", [int(x) for x in st[:, 0]], "mean rho", [round(float(x), 3) for x in st[:, 1]], "->",
+                  [round(float(x), 3) for x in st[:, 2]], "accepted steps", [None if np.isnan(x) else int(x) for x in st[:, 3]])
+        if search:
+            got = world.search(pmap, last, K, width, height, resect={})
+            ctx.synchronize()
+            found, st = got["n_corr"].cpu().numpy(), got["stats"].cpu().numpy()
+            seen = [int((last["xy"][t, :int(last["n"][t])].isfinite().all(1)).sum()) for t in range(tracks)]
+            print("search by projection, last frame against the whole map: found / keypoints seen per track",
+                  [f"{int(found[t])} / {seen[t]}" for t in range(tracks)], "(links of the last step:", v["links"][:, frames - 1].tolist(), ")")
+            print("  resected against them: participants", [int(x) for x in st[:, 0]], "mean rho", [round(float(x), 3) for x in st[:, 1]], "->",
                   [round(float(x), 3) for x in st[:, 2]], "accepted steps", [None if np.isnan(x) else int(x) for x in st[:, 3]])
     pmap.close()
     if with_world:

@@ -10,6 +10,7 @@
 #include "../vslam_amd.h"
 #include "../vslam_resect.h"
 #include "../vslam_adjust.h"
+#include "../vslam_search.h"
 
 namespace vslam {
 
@@ -74,6 +75,18 @@ public:
     void adjust(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, int window = 8,
                 const vslam_adjust_params *params = nullptr, double *d_stats = nullptr) {
         check(vslam_world_adjust(ctx_, world_, map, d_xy, xy_frames, h_K, window, params, d_stats), "vslam_world_adjust");
+    }
+    // Every track's world points searched by projection in the caller's latest frame, from the pose of the last frame recorded
+    // (vslam_world_search, include/vslam_search.h).  The world must be the one attached to `map`; d_xy_cur / d_desc_cur / d_n_cur
+    // [tracks][kp_stride]; search: nullptr for the defaults; resect: nullptr to search only, otherwise the frame's pose is
+    // resected against what was found and written back where that moved it.  d_corr_point / d_corr_kp [tracks][kp_stride],
+    // d_n_corr [tracks]; d_stats [tracks][4] f64 (the resection's) or nullptr.
+    void search(vslam_map *map, const float *d_xy_cur, const uint8_t *d_desc_cur, const int32_t *d_n_cur, const float *h_K, int width,
+                int height, int32_t *d_corr_point, int32_t *d_corr_kp, int32_t *d_n_corr, const vslam_search_params *search = nullptr,
+                const vslam_resect_params *resect = nullptr, double *d_stats = nullptr) {
+        check(vslam_world_search(ctx_, world_, map, d_xy_cur, d_desc_cur, d_n_cur, h_K, width, height, search, resect, d_corr_point,
+                                 d_corr_kp, d_n_corr, d_stats),
+              "vslam_world_search");
     }
     vslam_world *handle() const { return world_; }
 

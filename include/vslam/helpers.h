@@ -8,6 +8,7 @@
 #include "../vslam_amd.h"
 #include "../vslam_resect.h"
 #include "../vslam_adjust.h"
+#include "../vslam_search.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -76,6 +77,17 @@ void resect_poses(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const 
 void adjust_windows(vslam_ctx *ctx, f64 *d_R, f64 *d_T, const s32 *d_n_cams, int cam_stride, f64 *d_points, const s32 *d_n_points,
                     int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const float *d_obs_xy, int obs_stride, int batch,
                     const cv::Mat &K, f64 *d_stats = nullptr, const vslam_adjust_params *params = nullptr);
+
+// Search by projection for a batch of items the caller holds on the device (vslam_search_projection, include/vslam_search.h: the
+// arrays and strides are that call's): each item's points projected with its pose and matched to the frame's keypoints by
+// descriptor inside a pixel window, one-to-one, compacted into the layout resect_poses reads.  K: 3 x 3 CV_32F; params:
+// nullptr for the defaults; d_kp_taken, d_corr_point, d_corr_kp, d_stats may be nullptr.  Stream-ordered on `ctx`; throws
+// std::runtime_error with vslam_last_error.
+void search_projection(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets,
+                       const unsigned char *d_obs_desc, int obs_stride, const f64 *d_R, const f64 *d_T, const cv::Mat &K, int width, int height,
+                       const float *d_xy, const unsigned char *d_desc, const s32 *d_n_kp, int kp_stride, const s32 *d_kp_taken, int batch,
+                       s32 *d_kp_of_point, s32 *d_dist, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_point, s32 *d_corr_kp,
+                       s32 *d_n_corr, s32 *d_stats = nullptr, const vslam_search_params *params = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

@@ -89,6 +89,27 @@ class AdjustParams(C.Structure):   # vslam_adjust_params
         return p
 
 
+# every symbol include/vslam_search.h declares (a header of its own; tests/test_gpu_search.py checks it)
+SEARCH_SYMBOLS = ["vslam_search_params_default", "vslam_search_projection", "vslam_map_observation_descriptors", "vslam_world_search"]
+
+
+class SearchParams(C.Structure):   # vslam_search_params
+    _fields_ = [("radius_px", C.c_double), ("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
+
+    @classmethod
+    def make(cls, lib, **fields):
+        """vslam_search_params_default with `fields` written over it"""
+        p = cls()
+        rc = lib.vslam_search_params_default(C.byref(p))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_search_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"vslam_search_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -467,6 +488,46 @@ class Context:
                                                   C.c_int(P), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_xy), C.c_int(O), C.c_int(B),
                                                   Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
         return R, T, points, stats
+
+    def search_projection(self, points, n_points, obs_offsets, obs_desc, R, T, K, width, height, xy, desc, n_kp, kp_taken=None,
+                          out=None, want_indices=True, want_stats=True, **params):
+        """vslam_search_projection (include/vslam_search.h): each item's points (B, S, 4) f32, n_points (B,) i32 of them, with their
+        observation descriptors in CSR (obs_offsets (B, S + 1) i32, obs_desc (B, O, 32) u8), projected with R (B, 9) / T (B, 3) f64
+        and K (the 3 x 3 camera matrix, host) into a width x height frame with keypoints xy (B, Kp, 2) f32, desc (B, Kp, 32) u8, n_kp
+        (B,) i32; kp_taken (B, Kp) i32 or None; params: fields of vslam_search_params over its defaults.  out: a dict of output
+        tensors to write into (missing ones are made, zero-filled).  Returns the dict: kp_of_point, dist (B, S) i32; corr_points
+        (B, Kp, 3) f64; corr_xy (B, Kp, 2) f32; corr_point, corr_kp (B, Kp) i32 (want_indices); n_corr (B,) i32; stats (B, 4) i32
+        (want_stats) -- the layout resect_poses reads."""
+        import numpy as np
+        torch = self.torch
+        B, S, _ = points.shape
+        Kp, O = xy.shape[1], obs_desc.shape[1]
+        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
+                          (obs_desc, torch.uint8, "obs_desc"), (R, torch.float64, "R"), (T, torch.float64, "T"), (xy, torch.float32, "xy"),
+                          (desc, torch.uint8, "desc"), (n_kp, torch.int32, "n_kp"), (kp_taken, torch.int32, "kp_taken")):
+            self._dev(x, dt, nm)
+        if tuple(obs_offsets.shape) != (B, S + 1):
+            raise ValueError(f"obs_offsets has shape {tuple(obs_offsets.shape)}, not {(B, S + 1)}")
+        shapes = dict(kp_of_point=((B, S), torch.int32), dist=((B, S), torch.int32), corr_points=((B, Kp, 3), torch.float64),
+                      corr_xy=((B, Kp, 2), torch.float32), n_corr=((B,), torch.int32))
+        if want_indices:
+            shapes.update(corr_point=((B, Kp), torch.int32), corr_kp=((B, Kp), torch.int32))
+        if want_stats:
+            shapes.update(stats=((B, 4), torch.int32))
+        o = dict(out or {})
+        for k, (shape, dt) in shapes.items():
+            if k not in o:
+                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
+            self._dev(o[k], dt, k)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        prm = SearchParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_search_projection(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_desc), C.c_int(O), _ptr(R), _ptr(T),
+            Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height), _ptr(xy), _ptr(desc), _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken),
+            C.c_int(B), C.byref(prm), _ptr(o["kp_of_point"]), _ptr(o["dist"]), _ptr(o["corr_points"]), _ptr(o["corr_xy"]),
+            _ptr(o.get("corr_point")), _ptr(o.get("corr_kp")), _ptr(o["n_corr"]), _ptr(o.get("stats"))))
+        return o
 
     def kdtree_build(self, xy, n):
         torch = self.torch
@@ -936,6 +997,18 @@ class PointMap:
         self.ctx._check(self.lib.vslam_map_observations(self.ctx.handle, self.handle, _ptr(off), _ptr(fr), _ptr(pt)))
         return off, fr, pt
 
+    def observation_descriptors(self):
+        """vslam_map_observation_descriptors (include/vslam_search.h): (offsets [tracks][map_capacity + 1] i32, desc
+        [tracks][obs_capacity][32] u8) as cuda tensors, stream-ordered: row o is the descriptor of the observation that
+        observations() puts at row o; rows past a track's total are zero."""
+        torch = self.ctx.torch
+        dev = self.ctx.device
+        off = torch.zeros((self.tracks, self.map_capacity + 1), dtype=torch.int32, device=dev)
+        desc = torch.zeros((self.tracks, self.obs_capacity, 32), dtype=torch.uint8, device=dev)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_map_observation_descriptors(self.ctx.handle, self.handle, _ptr(off), _ptr(desc)))
+        return off, desc
+
     def close(self):
         """Before the context's close(): vslam_map_destroy waits for the context's stream.  After it the map is not touched
         (the handle is dropped; a context that is gone cannot be waited for)."""
@@ -984,6 +1057,32 @@ class World:
         self.ctx._check(self.lib.vslam_world_adjust(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), C.c_int(xy_frames),
                                                     Kh.ctypes.data_as(C.c_void_p), C.c_int(window), C.byref(prm), _ptr(stats)))
         return stats
+
+    def search(self, pmap, cur, K, width, height, resect=None, **params):
+        """vslam_world_search (include/vslam_search.h): every track's world points searched by projection, from the pose of the last
+        frame recorded, in the frame `cur` (a dict of xy (tracks, kp_stride, 2) f32, desc (tracks, kp_stride, 32) u8, n (tracks,)
+        i32); this world must be the one attached to `pmap`.  params: fields of vslam_search_params over its defaults.  resect:
+        None (search only: nothing but the outputs is written), or a dict of vslam_resect_params fields ({} for the defaults): the
+        frame's pose is then resected against what was found and, where that moved it, written back with the carry.  Returns a
+        dict of cuda tensors: corr_point, corr_kp (tracks, kp_stride) i32, n_corr (tracks,) i32 and, with resect, stats
+        (tracks, 4) f64."""
+        import numpy as np
+        torch = self.ctx.torch
+        xy, desc, n = (self.ctx._dev(cur[k], dt, k) for k, dt in (("xy", torch.float32), ("desc", torch.uint8), ("n", torch.int32)))
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        out = dict(corr_point=torch.zeros((self.tracks, self.kp_stride), dtype=torch.int32, device=xy.device),
+                   corr_kp=torch.zeros((self.tracks, self.kp_stride), dtype=torch.int32, device=xy.device),
+                   n_corr=torch.zeros((self.tracks,), dtype=torch.int32, device=xy.device))
+        if resect is not None:
+            out["stats"] = torch.zeros((self.tracks, 4), dtype=torch.float64, device=xy.device)
+        sprm = SearchParams.make(self.lib, **params)
+        rprm = ResectParams.make(self.lib, **resect) if resect is not None else None
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_search(
+            self.ctx.handle, self.handle, pmap.handle, _ptr(xy), _ptr(desc), _ptr(n), Kh.ctypes.data_as(C.c_void_p), C.c_int(width),
+            C.c_int(height), C.byref(sprm), C.byref(rprm) if rprm is not None else C.c_void_p(0), _ptr(out["corr_point"]),
+            _ptr(out["corr_kp"]), _ptr(out["n_corr"]), _ptr(out.get("stats"))))
+        return out
 
     def set_resection(self, enable=True, **params):
         """vslam_world_set_resection (include/vslam_resect.h), allowed at frame 0 only: from now on step() takes xy_cur and K

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "ctx.h"
+#include "../../include/vslam_search.h"
 
 struct vslam_map {
     vslam_ctx *ctx = nullptr;
@@ -650,6 +651,19 @@ int vslam_map_observations(vslam_ctx *ctx, vslam_map *map, int32_t *d_offsets, i
     map_offsets_kernel<<<map->tracks, kMT, 0, ctx->stream>>>(map->obs_cnt, map->sizes, map->map_capacity, map->map_capacity, d_offsets);
     map_csr_kernel<<<dim3(vs_div_up(2 * map->obs_capacity, kMT), map->tracks), kMT, 0, ctx->stream>>>(d, nullptr, map->sizes, d_offsets,
                                                                                                    nullptr, d_frame_ids, d_point_ids);
+    VS_HIP(ctx, hipGetLastError());
+    return VSLAM_OK;
+}
+
+int vslam_map_observation_descriptors(vslam_ctx *ctx, vslam_map *map, int32_t *d_offsets, uint8_t *d_desc) {
+    if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, map && map->ctx == ctx && d_offsets && d_desc, VSLAM_ERR_INVALID);
+    VS_ALIGNED(ctx, d_offsets, 4);
+    VS_ALIGNED(ctx, d_desc, 16);   // descriptor rows move as uint4 pairs
+    const MapDev d = dev_of(map);
+    map_offsets_kernel<<<map->tracks, kMT, 0, ctx->stream>>>(map->obs_cnt, map->sizes, map->map_capacity, map->map_capacity, d_offsets);
+    map_csr_kernel<<<dim3(vs_div_up(2 * map->obs_capacity, kMT), map->tracks), kMT, 0, ctx->stream>>>(d, nullptr, map->sizes, d_offsets,
+                                                                                                   d_desc, nullptr, nullptr);
     VS_HIP(ctx, hipGetLastError());
     return VSLAM_OK;
 }

@@ -874,6 +874,20 @@ void adjust_windows(vslam_ctx *ctx, f64 *d_R, f64 *d_T, const s32 *d_n_cams, int
                                         d_obs_xy, obs_stride, batch, k, params, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_adjust_windows: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void search_projection(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets,
+                       const unsigned char *d_obs_desc, int obs_stride, const f64 *d_R, const f64 *d_T, const cv::Mat &K, int width, int height,
+                       const float *d_xy, const unsigned char *d_desc, const s32 *d_n_kp, int kp_stride, const s32 *d_kp_taken, int batch,
+                       s32 *d_kp_of_point, s32 *d_dist, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_point, s32 *d_corr_kp,
+                       s32 *d_n_corr, s32 *d_stats, const vslam_search_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("search_projection: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_search_projection(ctx, d_points, d_n_points, pt_stride, d_obs_offsets, d_obs_desc, obs_stride, d_R, d_T, k, width,
+                                           height, d_xy, d_desc, d_n_kp, kp_stride, d_kp_taken, batch, params, d_kp_of_point, d_dist,
+                                           d_corr_points, d_corr_xy, d_corr_point, d_corr_kp, d_n_corr, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_search_projection: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
