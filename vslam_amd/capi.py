@@ -323,6 +323,17 @@ class Context:
         self._check(self.lib.vslam_debug_ransac_prune_x(self.handle, _ptr(x), C.c_int(batch), C.c_int(hyp)))
         return x
 
+    def debug_ransac_head(self, batch, hyp):
+        """(experiments build only) of this context's last RANSAC scoring: pot0 as ransac_screen_kernel left it, (batch, hyp)
+        int32, and the routing word per pair, (batch,) int32: 1 = the head on the prune certificate, 0 = on the cheap evaluation,
+        -1 = too few matches."""
+        torch = self.torch
+        pot0 = torch.zeros((batch, hyp), dtype=torch.int32, device="cuda")
+        route = torch.zeros((batch,), dtype=torch.int32, device="cuda")
+        self._ready()
+        self._check(self.lib.vslam_debug_ransac_head(self.handle, _ptr(pot0), _ptr(route), C.c_int(batch), C.c_int(hyp)))
+        return pot0, route
+
     def debug_ransac_prune_tile(self, F, xy):
         """(experiments build only) one 32 x 32 tile through ransac_prune's operand and accumulator mapping: F (32, 9), xy (4, 32)
         = x1, y1, x2, y2 -> n, a0 as (hypothesis, match) f32."""

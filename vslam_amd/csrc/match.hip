@@ -360,12 +360,24 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_mfma_kernel(
 // in four K = 64 steps at twice the int8 form's rate, with half the operand registers and half the LDS traffic.  Every
 // product is +-1 and every partial sum an integer below 2^9: the f32 accumulation is exact, so distances, indices and
 // the tie order are those of the other two kernels.  The running two best per (lane, row) are float keys
-// dot * 16384 - train index (exact: below 2^23), largest first = smallest distance, then lowest index: one v_fma_f32,
-// one v_med3_f32 and one v_max_f32 per result.  Layout (tools/mfma_fp4_probe.hip checks it on the device): A lane l = row
+// dot * 16384 - train index (exact: below 2^23), largest first = smallest distance, then lowest index: one v_med3_f32 and
+// one v_max_f32 per result, behind whatever the key itself costs (KF below).  Layout (tools/mfma_fp4_probe.hip checks it on the device): A lane l = row
 // l & 31, B lane l = column l & 31, each carrying 32 positions of the step chosen by l >> 5; D as for the int8 form.
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 constexpr int kFStride = 144;          // bytes per expanded train row in LDS: 128 + 16 (as kMStride: rows spread over the banks)
+// How a key is formed (KF; all four give the same float bit for bit, tools/mfma_fp4_probe.hip checks them on the device):
+//   0  unit block scales, key = fma(dot, 16384, -index): one v_fma_f32 per result (the form of rounds 4 to 8)
+//   1  block scales 2^7 x 2^7 on the descriptor steps: the accumulator holds dot * 16384, one v_add_f32 per result
+//   2  as 1, and a fifth K-step per tile adds -index on the matrix pipe: A = +1.0 nibbles, B = the train row's index chunk
+//      (index_chunk below: 32 more bytes per row behind its 128 spread ones, written by match_spread_kernel) -- nothing per
+//      result; only with pre-spread rows
+//   3  as 1, with -index as the C operand of the tile's first step: one v_mov_b32 per accumulator register and tile
+constexpr int kFKeyForm = 0;           // the product's: forms 1 to 3 are exact and none is faster (profiles/r09_matrix_pipe_ab.txt section 2)
+constexpr int kFRowBytes2 = 160;       // form 2: a spread train row in memory, 128 + 32
+constexpr int kFStride2 = 176;         // form 2: and in LDS, 160 + 16 (two buffers of two tiles: 22 KiB)
+constexpr int kFScale7 = 0x86868686;   // E8M0 2^7 (byte 0 is the one the instruction reads)
+constexpr int kFScale0 = 0x7F7F7F7F;   // E8M0 2^0
 constexpr float kFScale = 16384.f;     // VSLAM_MAX_KP: the index occupies the low 14 bits of a key
 constexpr float kFPad = 33554432.f;    // "index" of a train row beyond nt: below every key of a real row
 constexpr float kFNone = -67108864.f;  // no candidate yet
@@ -386,22 +398,43 @@ __device__ __forceinline__ v4i spread32_pm1(uint32_t w) {       // 32 bits -> 32
     return r;
 }
 __device__ __forceinline__ float med3_f32(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
+// -v, 0 <= v <= 127, as 32 E2M1 nibbles that sum to it: v / 6 times -6.0 (0xF), then the remainder as -1.0 (0xA), -2.0 (0xC),
+// -3.0 (0xD), -4.0 (0xE) or -4.0 and -1.0; the rest +0.0.  At most 23 nibbles are used.
+__device__ __forceinline__ v4i index_chunk(int v) {
+    const int q = v / 6, rem = v - 6 * q;
+    const uint32_t code = (0x00EEDCA0u >> (4 * rem)) & 0xFu, extra = rem == 5 ? 0xAu : 0u;
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int n = min(max(q - 8 * k, 0), 8);                  // sixes in this dword
+        w[k] = n == 8 ? 0xFFFFFFFFu : (1u << (4 * n)) - 1u;
+        if ((q >> 3) == k) w[k] |= code << (4 * (q & 7));
+        if (((q + 1) >> 3) == k) w[k] |= extra << (4 * ((q + 1) & 7));
+    }
+    return v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+}
 
 // The train descriptors of a pair spread to +-1 nibbles once (128 bytes per row) instead of by every workgroup that
 // streams them: seven workgroups of a pair at 2000 keypoints would each redo the same spreading, a quarter of the
 // matcher's vector instructions.  Row stride 128 bytes, kp_pad rows per pair (a multiple of the tile height).
+// IDX (key form 2): rows of kFRowBytes2 bytes, the last 32 the row's index chunk: index & 127 in the 16 bytes the lower lanes
+// of the fifth K-step carry (block scale 2^0), index >> 7 in the upper lanes' (block scale 2^7).
+template <bool IDX>
 __global__ __launch_bounds__(256) void match_spread_kernel(const uint8_t *__restrict__ desc2, const int32_t *__restrict__ n2,
                                                            int kp_stride, int kp_pad, uint8_t *__restrict__ tx) {
+    constexpr int kRow = IDX ? kFRowBytes2 : 128;
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;   // dword i & 7 of row i >> 3
     const int row = i >> 3;
     if (row >= n2[b]) return;
     const uint32_t w = reinterpret_cast<const uint32_t *>(desc2 + (size_t)b * kp_stride * VSLAM_DESC_BYTES)[i];
-    *reinterpret_cast<v4i *>(tx + ((size_t)b * kp_pad + row) * 128 + (size_t)(i & 7) * 16) = spread32_pm1(w);
+    uint8_t *dst = tx + ((size_t)b * kp_pad + row) * kRow;
+    *reinterpret_cast<v4i *>(dst + (size_t)(i & 7) * 16) = spread32_pm1(w);
+    if (IDX && (i & 7) < 2) *reinterpret_cast<v4i *>(dst + 128 + 16 * (i & 7)) = index_chunk((i & 7) ? row >> 7 : row & 127);
 }
 
 // PRE: the train rows come spread already (tx, match_spread_kernel); otherwise the workgroup spreads them itself.
 // CT = train tiles per trip of the main loop (one barrier per trip; 2 only with PRE).
-template <int RT, bool PRE, int CT>
+template <int RT, bool PRE, int CT, int KF>
 __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
     const uint8_t *__restrict__ desc1, const int32_t *__restrict__ n1, const uint8_t *__restrict__ desc2,
     const int32_t *__restrict__ n2, int kp_stride, int32_t *__restrict__ sel, int32_t *__restrict__ knn,
@@ -419,7 +452,11 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
     if (qbase >= nq) return;   // uniform for the whole workgroup
 
     static_assert(CT == 1 || PRE, "two tiles per trip only with pre-spread train rows");
-    __shared__ __align__(16) uint8_t s_b[2][CT * kMT * kFStride];
+    static_assert(KF >= 0 && KF <= 3 && (KF != 2 || PRE), "the index chunks come from match_spread_kernel");
+    static_assert(VSLAM_MAX_KP <= 16384, "index chunks: index >> 7 <= 127");
+    constexpr int kStride = KF == 2 ? kFStride2 : kFStride, kRow = KF == 2 ? kFRowBytes2 : 128;
+    constexpr int kScale = KF == 0 ? kFScale0 : kFScale7;   // of both operands of the descriptor steps
+    __shared__ __align__(16) uint8_t s_b[2][CT * kMT * kStride];
     const uint32_t *q32 = reinterpret_cast<const uint32_t *>(desc1 + (size_t)b * kp_stride * VSLAM_DESC_BYTES);
     const uint32_t *t32 = reinterpret_cast<const uint32_t *>(desc2 + (size_t)b * kp_stride * VSLAM_DESC_BYTES);
     int32_t *sel_b = sel + (size_t)b * kp_stride;
@@ -455,17 +492,21 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
     const int srow = st >> 3, sd = st & 7;
     // what a thread carries from global memory to LDS per tile: its packed dword, or (PRE) its 16 (8) spread bytes; rows beyond
     // nt are never initialised in tx -- any nibble pattern is a finite number, and those columns' keys carry kFPad
+    // (form 2: the tile's 32 index chunks, 1 KiB, are carried by one wave per tile of the trip: lane l 16 bytes of row l >> 1)
     struct Stage {
         uint4 v[CT];
+        uint4 x;
     };
-    const uint8_t *txb = PRE ? tx + (size_t)b * kp_pad * 128 + (size_t)srow * 128 + sd * 16 + (kSplit ? 8 * shalf : 0) : nullptr;
+    const uint8_t *txb = PRE ? tx + (size_t)b * kp_pad * kRow + (size_t)srow * kRow + sd * 16 + (kSplit ? 8 * shalf : 0) : nullptr;
+    const bool xmine = KF == 2 && wave < CT;   // wave-uniform
+    const int xoff = (wave * kMT + (lane >> 1)), xb = 128 + 16 * (lane & 1);
     auto fetch = [&](int trip) -> Stage {
         Stage st_;
 #pragma unroll
         for (int c = 0; c < CT; c++) {
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (PRE) {
-                const uint8_t *src = txb + (size_t)(trip * CT + c) * (kMT * 128);
+                const uint8_t *src = txb + (size_t)(trip * CT + c) * (kMT * kRow);
                 if (kSplit) {
                     const uint2 h = *reinterpret_cast<const uint2 *>(src);
                     v.x = h.x;
@@ -479,13 +520,15 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
             }
             st_.v[c] = v;
         }
+        st_.x = make_uint4(0u, 0u, 0u, 0u);
+        if (xmine) st_.x = *reinterpret_cast<const uint4 *>(tx + ((size_t)b * kp_pad + (size_t)trip * CT * kMT + xoff) * kRow + xb);
         return st_;
     };
     auto expand = [&](const Stage &st_, int buf) {
 #pragma unroll
         for (int c = 0; c < CT; c++) {
             const uint4 v = st_.v[c];
-            uint8_t *dst = &s_b[buf][(c * kMT + srow) * kFStride + sd * 16];
+            uint8_t *dst = &s_b[buf][(c * kMT + srow) * kStride + sd * 16];
             if (PRE) {
                 if (kSplit) *reinterpret_cast<uint2 *>(dst + 8 * shalf) = make_uint2(v.x, v.y);
                 else *reinterpret_cast<uint4 *>(dst) = v;
@@ -496,6 +539,7 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
                 *reinterpret_cast<v4i *>(dst) = spread32_pm1(v.x);
             }
         }
+        if (xmine) *reinterpret_cast<uint4 *>(&s_b[buf][xoff * kStride + xb]) = st_.x;
     };
 
     // (A software pipeline over the tiles -- three LDS buffers, the multiplies of tile i + 1 issued in front of the bookkeeping
@@ -511,29 +555,63 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
         if (trip + 1 < ntrips) expand(w_next, buf ^ 1);   // the other buffer was last read two barriers ago
         if (trip + 2 < ntrips) w_next = fetch(trip + 2);
         v16f acc[CT][RT];
+        float nidx[CT];   // -index of the lane's train column; a column beyond nt: below every key of a real row
+#pragma unroll
+        for (int c = 0; c < CT; c++) {
+            const int t = (trip * CT + c) * kMT + r;
+            nidx[c] = t < nt ? -(float)t : -kFPad;
+        }
 #pragma unroll
         for (int c = 0; c < CT; c++) {
 #pragma unroll
-            for (int rt = 0; rt < RT; rt++) acc[c][rt] = v16f{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            const uint8_t *src = &s_b[buf][(c * kMT + r) * kFStride + 16 * half];
+            for (int rt = 0; rt < RT; rt++) {
+                if (KF == 3) {
+#pragma unroll
+                    for (int g = 0; g < 16; g++) acc[c][rt][g] = nidx[c];
+                } else {
+                    acc[c][rt] = v16f{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                }
+            }
+            const uint8_t *src = &s_b[buf][(c * kMT + r) * kStride + 16 * half];
 #pragma unroll
             for (int s = 0; s < 4; s++) {
                 const v4i bq = *reinterpret_cast<const v4i *>(src + 32 * s);
                 const v8i bv = v8i{bq.x, bq.y, bq.z, bq.w, 0, 0, 0, 0};
 #pragma unroll
                 for (int rt = 0; rt < RT; rt++)
-                    acc[c][rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[rt][s], bv, acc[c][rt], 4, 4, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+                    acc[c][rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[rt][s], bv, acc[c][rt], 4, 4, 0, kScale, 0, kScale);
             }
+            if (KF == 2) {   // the fifth step: + 1.0 x (-index), the lower lanes' half at 2^0, the upper lanes' at 2^7
+                const v4i bq = *reinterpret_cast<const v4i *>(src + 128);
+                const v8i bv = v8i{bq.x, bq.y, bq.z, bq.w, 0, 0, 0, 0};
+                const v8i ones = v8i{0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};
+                const int sidx = half ? kFScale7 : kFScale0;
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++)
+                    acc[c][rt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ones, bv, acc[c][rt], 4, 4, 0, kFScale0, 0, sidx);
+            }
+        }
+        if (KF == 2 && trip == ntrips - 1) {
+            // Only the last trip has columns beyond nt.  Their rows of tx were never written: descriptor nibbles and index chunk
+            // are whatever the memory held -- finite numbers all (E2M1 has no others), under fixed scales -- and their results
+            // are replaced here by "no candidate".  (A pad code under a large per-column scale would do the same on the matrix
+            // pipe at the price of a scale read per lane and tile, and of spreading the pad rows.)
+#pragma unroll
+            for (int c = 0; c < CT; c++)
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                    for (int g = 0; g < 16; g++) acc[c][rt][g] = nidx[c] == -kFPad ? kFNone : acc[c][rt][g];
         }
 #pragma unroll
         for (int c = 0; c < CT; c++) {
-            const int t = (trip * CT + c) * kMT + r;
-            const float nidx = t < nt ? -(float)t : -kFPad;   // key = dot * 16384 - index
 #pragma unroll
             for (int g = 0; g < 16; g++) {
 #pragma unroll
                 for (int rt = 0; rt < RT; rt++) {
-                    const float key = __builtin_fmaf(acc[c][rt][g], kFScale, nidx);
+                    // key = dot * 16384 - index
+                    const float key = KF == 0 ? __builtin_fmaf(acc[c][rt][g], kFScale, nidx[c])
+                                              : (KF == 1 ? acc[c][rt][g] + nidx[c] : acc[c][rt][g]);
                     k2[rt][g] = med3_f32(k1[rt][g], k2[rt][g], key);
                     k1[rt][g] = fmaxf(k1[rt][g], key);
                 }
@@ -640,9 +718,10 @@ int vs_launch_match(vslam_ctx *ctx, const uint8_t *d1, const int32_t *n1, const 
         const int xgrid = vs_xcd_grid(batch, per_pair);
         const int kp_pad = vs_div_up(kp_stride, 2 * kMT) * 2 * kMT;
         uint8_t *tx = nullptr;
-        if ((rc = vs_arena_get(ctx, "match.spread", (size_t)batch * kp_pad * 128, (void **)&tx))) return rc;
-        match_spread_kernel<<<dim3(vs_div_up(kp_stride * 8, 256), batch), 256, 0, ctx->stream>>>(d2, n2, kp_stride, kp_pad, tx);
-        match_knn2_fp4_kernel<1, true, 2><<<xgrid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
+        constexpr bool kIdx = kFKeyForm == 2;
+        if ((rc = vs_arena_get(ctx, "match.spread", (size_t)batch * kp_pad * (kIdx ? kFRowBytes2 : 128), (void **)&tx))) return rc;
+        match_spread_kernel<kIdx><<<dim3(vs_div_up(kp_stride * 8, 256), batch), 256, 0, ctx->stream>>>(d2, n2, kp_stride, kp_pad, tx);
+        match_knn2_fp4_kernel<1, true, 2, kFKeyForm><<<xgrid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
     }
 #else
     static const bool popcount_path = VS_EXPERIMENT_ENV("VSLAM_MATCH_POPCOUNT") != nullptr;   // the vector-ALU kernel, for A/B timing
@@ -687,20 +766,39 @@ int vs_launch_match(vslam_ctx *ctx, const uint8_t *d1, const int32_t *n1, const 
                 static const char *const nopre = VS_EXPERIMENT_ENV("VSLAM_MATCH_NO_PRESPREAD");   // A/B timing: every workgroup spreads for itself
                 static const char *const ct_env = VS_EXPERIMENT_ENV("VSLAM_MATCH_TILES_PER_TRIP");
                 const int ct = ct_env ? atoi(ct_env) : 2;
+                // VSLAM_MATCH_KEY_FORM=0..3 (read at every call: a test switches it within a process): how the keys are formed, KF
+                // above; the product's form unless set.  Form 2 needs the index chunks of the pre-spread rows; the arrangement that
+                // spreads in place takes form 1 in its stead (and the product's form when that is not 2).
+                const char *const kf_env = VS_EXPERIMENT_ENV("VSLAM_MATCH_KEY_FORM");
+                const int kf = kf_env ? atoi(kf_env) : kFKeyForm;
+                VS_REQUIRE(ctx, kf >= 0 && kf <= 3, VSLAM_ERR_INVALID);
+#define VS_FP4_LAUNCH(RT_, PRE_, CT_, KF_, THREADS_, TX_, PAD_) \
+    match_knn2_fp4_kernel<RT_, PRE_, CT_, KF_><<<xgrid, THREADS_, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, TX_, PAD_, batch, per_pair)
+#define VS_FP4_FORMS(RT_, PRE_, CT_, THREADS_, TX_, PAD_)                                  \
+    do {                                                                                   \
+        if (kf == 0) VS_FP4_LAUNCH(RT_, PRE_, CT_, 0, THREADS_, TX_, PAD_);                \
+        else if (kf == 3) VS_FP4_LAUNCH(RT_, PRE_, CT_, 3, THREADS_, TX_, PAD_);           \
+        else if (kf == 2 && PRE_) VS_FP4_LAUNCH(RT_, PRE_, CT_, (PRE_ ? 2 : 1), THREADS_, TX_, PAD_); \
+        else VS_FP4_LAUNCH(RT_, PRE_, CT_, 1, THREADS_, TX_, PAD_);                        \
+    } while (0)
                 if (!nopre) {
                     const int kp_pad = vs_div_up(kp_stride, 2 * kMT) * 2 * kMT;
                     uint8_t *tx = nullptr;
-                    if ((rc = vs_arena_get(ctx, "match.spread", (size_t)batch * kp_pad * 128, (void **)&tx))) return rc;
-                    match_spread_kernel<<<dim3(vs_div_up(kp_stride * 8, 256), batch), 256, 0, ctx->stream>>>(d2, n2, kp_stride, kp_pad, tx);
-                    if (wide4 && ct == 2) match_knn2_fp4_kernel<2, true, 2><<<xgrid, 256, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
-                    else if (wide4) match_knn2_fp4_kernel<2, true, 1><<<xgrid, 256, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
-                    else if (ct == 2) match_knn2_fp4_kernel<1, true, 2><<<xgrid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
-                    else match_knn2_fp4_kernel<1, true, 1><<<xgrid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, tx, kp_pad, batch, per_pair);
+                    if ((rc = vs_arena_get(ctx, "match.spread", (size_t)batch * kp_pad * kFRowBytes2, (void **)&tx))) return rc;
+                    const dim3 sgrid(vs_div_up(kp_stride * 8, 256), batch);
+                    if (kf == 2) match_spread_kernel<true><<<sgrid, 256, 0, ctx->stream>>>(d2, n2, kp_stride, kp_pad, tx);
+                    else match_spread_kernel<false><<<sgrid, 256, 0, ctx->stream>>>(d2, n2, kp_stride, kp_pad, tx);
+                    if (wide4 && ct == 2) VS_FP4_FORMS(2, true, 2, 256, tx, kp_pad);
+                    else if (wide4) VS_FP4_FORMS(2, true, 1, 256, tx, kp_pad);
+                    else if (ct == 2) VS_FP4_FORMS(1, true, 2, 512, tx, kp_pad);
+                    else VS_FP4_FORMS(1, true, 1, 512, tx, kp_pad);
                 } else if (wide4) {
-                    match_knn2_fp4_kernel<2, false, 1><<<xgrid, 256, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, nullptr, 0, batch, per_pair);
+                    VS_FP4_FORMS(2, false, 1, 256, nullptr, 0);
                 } else {
-                    match_knn2_fp4_kernel<1, false, 1><<<xgrid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, nullptr, 0, batch, per_pair);
+                    VS_FP4_FORMS(1, false, 1, 512, nullptr, 0);
                 }
+#undef VS_FP4_FORMS
+#undef VS_FP4_LAUNCH
             } else if (wide) match_knn2_mfma_kernel<2><<<grid, 256, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn);
             else match_knn2_mfma_kernel<1><<<grid, 512, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn);
         }

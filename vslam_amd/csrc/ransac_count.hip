@@ -7,6 +7,7 @@
 // Numerics: the counts handed on are the reference's counts, bit for bit, for every hypothesis that reaches the pair's
 // maximum count (all others report -1).  The cheap evaluation only decides what its certified error band allows; anything
 // inside the band is decided by the exact sequence (residual_e, ransac_residual.h).  The derivation stands in front of the code.
+#include "ransac_prune_tile.h"
 #include "ransac_residual.h"
 
 namespace {
@@ -124,7 +125,7 @@ static_assert(VSLAM_MAX_KP <= 65536, "queue words keep the match index in 16 bit
 __host__ __device__ constexpr int cnt_pad(int n) { return (n + 255) & ~255; }
 // The word the screen hands on per hypothesis beside pot0: the head's certain inliers (g < lo), kHeadUncertified where
 // nothing of the head is certified, and the sum of the head's cheap values.
-constexpr int kHeadUncertified = -1;
+constexpr int kHeadUncertified = kVsHeadUncertified;
 // relative error of a cheap sum against the sum of its terms: 12 u per term (g against e, see ransac_ties_kernel) and u per
 // float addition on the longest path to the total (`adds`).  2^-18 = 64 u covers 51 additions, i.e. 21 sub-blocks (about
 // 5500 matches); beyond that the term grows with the walk instead of being assumed.
@@ -500,15 +501,37 @@ __global__ __launch_bounds__(kRankThreads) void ransac_rank_kernel(
 // kHeadUncertified after a zero / denormal / NaN dd; the sum of the head's cheap values): the count kernel starts behind
 // the head with these and evaluates the head again only for a hypothesis that completes with pot0 != certain.
 // Workgroup = 128 hypotheses, a wave walks 32 of them with two of the ranked matches per lane.  grid = (ceil(hyp / 128), batch).
-__global__ __launch_bounds__(256) void ransac_screen_kernel(
+// route_out (experiments build only): per pair, 1 = the certificate, 0 = the cheap evaluation, -1 = fewer than min_m matches.
+#ifdef VSLAM_EXPERIMENTS
+#define VS_SCREEN_ROUTE_PARAM , int32_t *__restrict__ route_out
+#else
+#define VS_SCREEN_ROUTE_PARAM
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void ransac_screen_kernel(
     const float *__restrict__ rk, int kp_pad, const int32_t *__restrict__ m_arr, int min_m, int kp_stride, int hyp,
     float threshold, const float *__restrict__ hypF, const float *__restrict__ cmax, const int32_t *__restrict__ cbound,
-    int32_t *__restrict__ pot0, int2 *__restrict__ head) {
+    int32_t *__restrict__ pot0, int2 *__restrict__ head, float splus, int route VS_SCREEN_ROUTE_PARAM) {
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hbase = blockIdx.x * kScreenHyps;
     const int m = min(m_arr[b], kp_stride);
+    const int bound_pilots = cbound[b];   // ransac_rank_kernel's: a count some hypothesis of the pair reaches (read beside m)
+#ifdef VSLAM_EXPERIMENTS
+    if (route_out && blockIdx.x == 0 && tid == 0)
+        route_out[b] = m < min_m ? -1 : (vs_head_on_certificate(m, bound_pilots, min(m, kScreenMatches), route) ? 1 : 0);
+#endif
     if (m < min_m) return;
+    // The pair's head on the prune certificate instead (workgroup-uniform; the same 4 waves x 32 hypotheses).  One kernel with
+    // this branch, not a launch of its own: a launch whose 8192 workgroups all return costs 0.006 to 0.012 ms
+    // (profiles/r09_matrix_pipe_ab.txt section 3).  Either path alone compiles to 68 vector registers; together the compiler
+    // took 108 (four waves per SIMD), and amdgpu_waves_per_eu(7, 7) above holds the kernel to 72 without a spill (section 4).
+    if (vs_head_on_certificate(m, bound_pilots, min(m, kScreenMatches), route)) {
+        static_assert(kScreenHyps == vs_prune::kPruneWaves * vs_prune::kPruneHyps && kScreenMatches <= vs_prune::kHeadTiles * vs_prune::kPruneTile,
+                      "a wave of the screen is a wave of the prune tile");
+        if (hbase + wave * 32 < hyp)   // wave-uniform
+            vs_prune::head_on_certificate(rk, kp_pad, b, m, min(m, kScreenMatches), hbase + wave * 32, hyp, threshold, splus, hypF, cmax, pot0, head);
+        return;
+    }
     __shared__ __align__(16) float s_rec[kScreenHyps * kCntRec];
     if (tid < kScreenHyps) {
         const float *src = hypF + ((size_t)b * hyp + min(hbase + tid, hyp - 1)) * 9;
@@ -519,7 +542,6 @@ __global__ __launch_bounds__(256) void ransac_screen_kernel(
         cnt_store_record(s_rec + tid * kCntRec, f, B);
     }
     const int n0 = min(m, kScreenMatches);
-    const int bound_pilots = cbound[b];   // ransac_rank_kernel's: a count some hypothesis of the pair reaches
     const float *r = rk + (size_t)b * 4 * kp_pad;
     const float2 x1 = *reinterpret_cast<const float2 *>(r + 2 * lane);
     const float2 y1 = *reinterpret_cast<const float2 *>(r + kp_pad + 2 * lane);
@@ -1031,11 +1053,29 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
         ransac_rank_kernel<<<batch, kRankThreads, 0, ctx->stream>>>(xy1, xy2, pairs, m, min_m, kp_stride, kp_pad, hyp, threshold, hypF,
                                                                     cbound, rk, cmax, sfloor);
     }
+    // the head of a pair: by the cheap evaluation (exact counts and sums handed on) or, where the hypotheses have to miss more
+    // than the head holds, by the prune certificate on the matrix cores (vs_head_on_certificate)
+    int route = -1;
+    if (const char *e = VS_EXPERIMENT_ENV("VSLAM_RANSAC_HEAD_ROUTE")) route = atoi(e) ? 1 : 0;   // the tests force either path (read at every call)
+#ifdef VSLAM_EXPERIMENTS
+    int32_t *route_out = nullptr, *pot0_out = nullptr;   // what vslam_debug_ransac_head (ransac_prune.hip) hands out
+    if ((rc = vs_arena_get(ctx, "ransac.head_route", sizeof(int32_t) * (size_t)batch, (void **)&route_out))) return rc;
+    if ((rc = vs_arena_get(ctx, "ransac.head_pot0", sizeof(int32_t) * (size_t)batch * hyp, (void **)&pot0_out))) return rc;
+#endif
     {
         VsProfScope ps(ctx, "ransac_screen_kernel");
         dim3 grid(vs_div_up(hyp, kScreenHyps), batch);
-        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head);
+#ifdef VSLAM_EXPERIMENTS
+        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
+                                                            pc_splus(threshold), route, route_out);
+#else
+        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
+                                                            pc_splus(threshold), route);
+#endif
     }
+#ifdef VSLAM_EXPERIMENTS   // pot0 as the screen leaves it, before ransac_prune marks the dead
+    VS_HIP(ctx, hipMemcpyAsync(pot0_out, pot0, sizeof(int32_t) * (size_t)batch * hyp, hipMemcpyDeviceToDevice, ctx->stream));
+#endif
     {
         VsProfScope ps(ctx, "ransac_cand_kernel");
         ransac_cand_kernel<<<batch, 64 * kCandMax, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, pot0,

@@ -24,7 +24,7 @@
 // of two hypotheses, and s_bcnt1 on each half counts their certified misses on the scalar unit.
 //
 // A hypothesis h with X[h] certified misses behind the head is dead when pot0[h] + (m - n0) - X[h] < cbound[pair]: pot0 bounds
-// its inliers on the head (ransac_screen_kernel), m - n0 - X[h] those behind it.  A dead hypothesis gets
+// its inliers on the head (ransac_screen_kernel, either path), m - n0 - X[h] those behind it.  A dead hypothesis gets
 // pot0[h] = -(m - n0) - 1, with which ransac_count_kernel's own `alive` test is false (cbound >= 0), and reports -1.  Nothing
 // else is written: survivors keep pot0 and head.  What the accept rule can see is unchanged by construction: a dead hypothesis is
 // below the pair's maximum count, and ransac_ties_kernel writes -1 for every such hypothesis whatever the count kernel found.
@@ -39,56 +39,16 @@
 // and once every live one has missed fewer than half of the matches seen so far -- a plateau of good hypotheses (easy data,
 // photographs), of which nothing can be pruned.  Both are looked at every 64 matches.  A row walks until its slowest
 // hypothesis is dead: on the hard data nearly every row goes 400 matches or more behind the head.
-#include "ransac_prune_cert.h"
-#include "ransac_residual.h"
+#include "ransac_prune_tile.h"
 
 namespace {
+using namespace vs_prune;
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-constexpr int kPruneWaves = 4;
-constexpr int kPruneHyps = 32;    // per wave: the rows of a tile
-constexpr int kPruneTile = 32;    // matches per tile: its columns
 constexpr int kPruneStep = 2;     // tiles between two looks at the stop rules
-constexpr int kPruneOGT = 2;      // __builtin_amdgcn_fcmpf: llvm::FCmpInst::FCMP_OGT
 // Chosen by measurement (profiles/r08_prune_ab.txt section 5, HISTORY.md round 8): a wave walks all matches behind the head
 // (limits of 256 and 512 were slower), and the plateau rule stops at half of the matches seen (3/4 and no rule: no gain).
 // The pair-level gate (in the kernel) can be switched off in the experiments build (VSLAM_RANSAC_PRUNE_GATE=0): the tests
 // walk the pairs it skips that way.
-
-// hypothesis row held by accumulator register r of a lane in half `half` (cdna4 ISA, 32x32 C/D layout)
-__host__ __device__ constexpr int prune_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// A lane's A operands for its hypothesis: lower half even k, upper half odd k; k = 9 (n) and k = 3 (a0) are the zero padding.
-struct PruneA {
-    float n[5], d[2];
-};
-__device__ __forceinline__ PruneA prune_operands(const float *f, bool half) {
-    PruneA A;
-#pragma unroll
-    for (int s = 0; s < 4; s++) A.n[s] = half ? f[2 * s + 1] : f[2 * s];
-    A.n[4] = half ? 0.f : f[8];
-    A.d[0] = half ? f[1] : f[0];
-    A.d[1] = half ? 0.f : f[2];
-    return A;
-}
-
-// One tile: n and a0 of 32 hypotheses x 32 matches.  The lane brings the coordinates of match (column) l & 31; phi_k for
-// k = 2 s + (l >> 5) is its B operand of step s.  The last two steps of n (x1 | y1, 1 | 0) are the two steps of a0.
-__device__ __forceinline__ void prune_tile(const PruneA &A, bool half, float x1, float y1, float x2, float y2, v16f &n, v16f &a0) {
-    const float p = x2 * (half ? y1 : x1);   // phi_0 | phi_1
-    const float q = y2 * (half ? x1 : y1);   // phi_4 | phi_3
-    const float b1 = half ? q : x2, b2 = half ? y2 : q, b3 = half ? y1 : x1, b4 = half ? 0.f : 1.f;
-    v16f z;
-#pragma unroll
-    for (int r = 0; r < 16; r++) z[r] = 0.f;
-    n = __builtin_amdgcn_mfma_f32_32x32x2f32(A.n[0], p, z, 0, 0, 0);
-    n = __builtin_amdgcn_mfma_f32_32x32x2f32(A.n[1], b1, n, 0, 0, 0);
-    n = __builtin_amdgcn_mfma_f32_32x32x2f32(A.n[2], b2, n, 0, 0, 0);
-    n = __builtin_amdgcn_mfma_f32_32x32x2f32(A.n[3], b3, n, 0, 0, 0);
-    n = __builtin_amdgcn_mfma_f32_32x32x2f32(A.n[4], b4, n, 0, 0, 0);
-    a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A.d[0], b3, z, 0, 0, 0);
-    a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A.d[1], b4, a0, 0, 0, 0);
-}
 
 #ifdef VSLAM_EXPERIMENTS
 #define VS_PRUNE_X_PARAM , int32_t *__restrict__ x_out
@@ -247,6 +207,20 @@ int vslam_debug_ransac_prune_x(vslam_ctx *ctx, int32_t *d_out, int batch, int hy
     const auto it = ctx->arena.find("ransac.prune_x");
     VS_REQUIRE(ctx, it != ctx->arena.end() && it->second.bytes >= bytes, VSLAM_ERR_INVALID);
     VS_HIP(ctx, hipMemcpyAsync(d_out, it->second.ptr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return VSLAM_OK;
+}
+// (experiments build only) of the last RANSAC scoring of this context: pot0 as ransac_screen_kernel's two paths left it
+// (batch x hyp int32, before the prune kernel) and the routing word per pair (1 = the head on the certificate, 0 = on the
+// cheap evaluation, -1 = fewer than min_m matches), copied in stream order
+int vslam_debug_ransac_head(vslam_ctx *ctx, int32_t *d_pot0, int32_t *d_route, int batch, int hyp) {
+    if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, d_pot0 && d_route && batch > 0 && hyp > 0 && vs_ptr_bits(d_pot0, d_route) % 4 == 0, VSLAM_ERR_INVALID);
+    const size_t bytes = sizeof(int32_t) * (size_t)batch * hyp;
+    const auto ip = ctx->arena.find("ransac.head_pot0"), ir = ctx->arena.find("ransac.head_route");
+    VS_REQUIRE(ctx, ip != ctx->arena.end() && ip->second.bytes >= bytes, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, ir != ctx->arena.end() && ir->second.bytes >= sizeof(int32_t) * (size_t)batch, VSLAM_ERR_INVALID);
+    VS_HIP(ctx, hipMemcpyAsync(d_pot0, ip->second.ptr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    VS_HIP(ctx, hipMemcpyAsync(d_route, ir->second.ptr, sizeof(int32_t) * (size_t)batch, hipMemcpyDeviceToDevice, ctx->stream));
     return VSLAM_OK;
 }
 // (experiments build only) one 32 x 32 tile through the kernel's own operand and accumulator mapping

@@ -76,3 +76,18 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
 int vs_launch_ransac_prune(vslam_ctx *ctx, const float *rk, int kp_pad, const int32_t *m, int min_m, int kp_stride, int hyp,
                            float threshold, const float *hypF, const float *cmax, const int32_t *cbound, int32_t *pot0, int batch,
                            int n_head);
+
+// The word the head's kernel hands on per hypothesis beside pot0 where nothing of the head is certified (ransac_count.hip).
+constexpr int kVsHeadUncertified = -1;
+
+// Which kernel forms pot0 on a pair's head (its n0 most-missed matches).  A pair whose hypotheses have to miss more matches
+// than the head holds -- the prune gate's form, with the pilots' bound that ransac_rank_kernel has stored by then, never
+// above the bound the gate sees: every pair the prune kernel walks is among them -- takes the certificate
+// (head_on_certificate, ransac_prune_tile.h: certified misses only, nothing exact handed on); every other pair takes the cheap
+// evaluation, whose exact head counts and sums its survivors live on.  route: -1 = by this rule, 0 / 1 = every pair to the
+// cheap evaluation / to the certificate (experiments build, VSLAM_RANSAC_HEAD_ROUTE).  ransac_screen_kernel branches on it per
+// workgroup.  (A pair without a match stays with the cheap evaluation: the certificate's lanes read ranked match m - 1 where
+// they have none of their own.)
+__host__ __device__ constexpr bool vs_head_on_certificate(int m, int bound, int n0, int route) {
+    return m > 0 && (route < 0 ? m - bound + 1 > n0 : route != 0);
+}
