@@ -4,7 +4,7 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect] [--adjust] [--search]] [output directory]
+    python examples/render_map.py [--world [--resect] [--adjust] [--search] [--relocalise]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
@@ -16,6 +16,11 @@ chained from the pair's fundamental matrix alone; the accepted steps and partici
 --search (with --world): after the last step (and after --adjust) the last frame is searched by projection against the WHOLE map
 of its track and resected against what was found (World.search, include/vslam_search.h); found / seen per track are printed,
 beside the links the step itself had.
+--relocalise (with --world, last of all): the recorded pose of the last frame is dropped to the identity, as if the track had been
+lost, and found again from the map alone (World.relocalise, include/vslam_pnp.h: descriptor match without a pose, P3P RANSAC,
+polish, write-back); the world is drawn with the dropped pose and with the one that came back (track*_before_relocalise.ppm /
+track*_after_relocalise.ppm) and matches / inliers / found per track are printed.  inlier_px 4 and 1024 hypotheses: on these
+synthetic tracks the defaults (2 px, 128) do not find every track; nothing here is tuned.
 """
 import os
 import sys
@@ -36,13 +41,14 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust", "--search")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust", "--search", "--relocalise")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
     adjust = "--adjust" in sys.argv[1:]
     search = "--search" in sys.argv[1:]
-    if (resect or adjust or search) and not with_world:
-        sys.exit("--resect, --adjust and --search need --world")
+    relocalise = "--relocalise" in sys.argv[1:]
+    if (resect or adjust or search or relocalise) and not with_world:
+        sys.exit("--resect, --adjust, --search and --relocalise need --world")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -118,6 +124,28 @@ def main():
                   [f"{int(found[t])} / {seen[t]}" for t in range(tracks)], "(links of the last step:", v["links"][:, frames - 1].tolist(), ")")
             print("  resected against them: participants", [int(x) for x in st[:, 0]], "mean rho", [round(float(x), 3) for x in st[:, 1]], "->",
                   [round(float(x), 3) for x in st[:, 2]], "accepted steps", [None if np.isnan(x) else int(x) for x in st[:, 3]])
+        if relocalise:
+            C = capi.C
+            a, f1 = world.arrays(), frames - 1
+            recorded = world.view()["Twc"][:, f1].copy()
+            eye4 = np.eye(4)
+            for t in range(tracks):                              # the last frame's pose dropped to the identity
+                for ptr, m in ((a.d_Twc + 8 * 16 * (t * frames + f1), eye4), (a.d_pose + 4 * 16 * (t * frames + f1), eye4.astype(np.float32))):
+                    m = np.ascontiguousarray(m)
+                    ctx._check(ctx.lib.vslam_copy_h2d(ctx.handle, C.c_void_p(ptr), C.c_void_p(m.ctypes.data), C.c_size_t(m.nbytes)))
+            world.render(pmap, view, W, H, out=(world_images, None))
+            before = world_images.cpu().numpy()
+            got = world.relocalise(pmap, last, K, hypotheses=1024, inlier_px=4.0)
+            world.render(pmap, view, W, H, out=(world_images, None))
+            ctx.synchronize()
+            after, back = world_images.cpu().numpy(), world.view()["Twc"][:, f1]
+            for t in range(tracks):
+                write_ppm(os.path.join(out_dir, f"track{t}_before_relocalise.ppm"), before[t])
+                write_ppm(os.path.join(out_dir, f"track{t}_after_relocalise.ppm"), after[t])
+            print("relocalised from the map alone: matches", got["n_corr"].cpu().numpy().tolist(), "inliers", got["n_inliers"].cpu().numpy().tolist(),
+                  "found", got["found"].cpu().numpy().tolist())
+            print("  camera centre, recorded -> relocalised, track 0:", [round(float(x), 3) for x in recorded[0, [3, 7, 11]]], "->",
+                  [round(float(x), 3) for x in back[0, [3, 7, 11]]])
     pmap.close()
     if with_world:
         world.close()

@@ -11,6 +11,7 @@
 #include "../vslam_resect.h"
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
+#include "../vslam_pnp.h"
 
 namespace vslam {
 
@@ -87,6 +88,19 @@ public:
         check(vslam_world_search(ctx_, world_, map, d_xy_cur, d_desc_cur, d_n_cur, h_K, width, height, search, resect, d_corr_point,
                                  d_corr_kp, d_n_corr, d_stats),
               "vslam_world_search");
+    }
+    // The pose of the caller's latest frame found from the map alone, for every track (vslam_world_relocalise, include/vslam_pnp.h):
+    // the world's points matched to the keypoints by descriptor, P3P RANSAC over the matches, the polish (nullptr: none), and for
+    // the tracks that were found the write-back of search().  The last recorded pose is not read.  The world must be the one
+    // attached to `map`; d_seeds [tracks]; match / pnp: nullptr for the defaults; d_found, d_winner, d_n_inliers, d_n_corr [tracks];
+    // d_corr_point / d_corr_kp [tracks][kp_stride]; d_stats [tracks][4] f64 (the polish's) or nullptr.
+    void relocalise(vslam_map *map, const float *d_xy_cur, const uint8_t *d_desc_cur, const int32_t *d_n_cur, const float *h_K,
+                    const uint32_t *d_seeds, int32_t *d_found, int32_t *d_winner, int32_t *d_n_inliers, int32_t *d_corr_point,
+                    int32_t *d_corr_kp, int32_t *d_n_corr, const vslam_resect_params *polish = nullptr, const vslam_pnp_params *pnp = nullptr,
+                    const vslam_match_params *match = nullptr, double *d_stats = nullptr) {
+        check(vslam_world_relocalise(ctx_, world_, map, d_xy_cur, d_desc_cur, d_n_cur, h_K, d_seeds, match, pnp, polish, d_found, d_winner,
+                                     d_n_inliers, d_corr_point, d_corr_kp, d_n_corr, d_stats),
+              "vslam_world_relocalise");
     }
     vslam_world *handle() const { return world_; }
 

@@ -9,6 +9,7 @@
 #include "../vslam_resect.h"
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
+#include "../vslam_pnp.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -88,6 +89,16 @@ void search_projection(vslam_ctx *ctx, const float *d_points, const s32 *d_n_poi
                        const float *d_xy, const unsigned char *d_desc, const s32 *d_n_kp, int kp_stride, const s32 *d_kp_taken, int batch,
                        s32 *d_kp_of_point, s32 *d_dist, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_point, s32 *d_corr_kp,
                        s32 *d_n_corr, s32 *d_stats = nullptr, const vslam_search_params *params = nullptr);
+
+// A pose without a prior for a batch of items the caller holds on the device (vslam_pnp_ransac, include/vslam_pnp.h: the arrays
+// and strides are that call's): P3P RANSAC over each item's 3-D / 2-D correspondences, d_R / d_T written where an item is found,
+// the winner's inliers compacted into the layout resect_poses reads.  K: 3 x 3 CV_32F; params: nullptr for the defaults; polish:
+// nullptr for none; d_corr_index, d_counts, d_stats may be nullptr.  Stream-ordered on `ctx`; throws std::runtime_error with
+// vslam_last_error.
+void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s32 *d_n, int batch, int stride, const cv::Mat &K,
+                const unsigned int *d_seeds, f64 *d_R, f64 *d_T, s32 *d_inlier, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_index,
+                s32 *d_n_inliers, s32 *d_winner, s32 *d_counts = nullptr, f64 *d_stats = nullptr, const vslam_pnp_params *params = nullptr,
+                const vslam_resect_params *polish = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

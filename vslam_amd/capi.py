@@ -110,6 +110,44 @@ class SearchParams(C.Structure):   # vslam_search_params
         return p
 
 
+# every symbol include/vslam_pnp.h declares (a header of its own; tests/test_pnp_lds.py checks it)
+PNP_SYMBOLS = ["vslam_pnp_params_default", "vslam_pnp_ransac", "vslam_match_params_default", "vslam_match_points", "vslam_world_relocalise"]
+
+
+class PnpParams(C.Structure):   # vslam_pnp_params
+    _fields_ = [("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("inlier_px", C.c_double)]
+
+    @classmethod
+    def make(cls, lib, **fields):
+        """vslam_pnp_params_default with `fields` written over it"""
+        p = cls()
+        rc = lib.vslam_pnp_params_default(C.byref(p))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_pnp_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"vslam_pnp_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class MatchParams(C.Structure):   # vslam_match_params
+    _fields_ = [("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
+
+    @classmethod
+    def make(cls, lib, **fields):
+        """vslam_match_params_default with `fields` written over it"""
+        p = cls()
+        rc = lib.vslam_match_params_default(C.byref(p))
+        if rc != OK:
+            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_match_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"vslam_match_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -538,6 +576,80 @@ class Context:
             Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height), _ptr(xy), _ptr(desc), _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken),
             C.c_int(B), C.byref(prm), _ptr(o["kp_of_point"]), _ptr(o["dist"]), _ptr(o["corr_points"]), _ptr(o["corr_xy"]),
             _ptr(o.get("corr_point")), _ptr(o.get("corr_kp")), _ptr(o["n_corr"]), _ptr(o.get("stats"))))
+        return o
+
+    def pnp_ransac(self, points, xy, n, K, seeds, R, T, polish=None, out=None, want_index=True, want_counts=False, want_stats=True,
+                   **params):
+        """vslam_pnp_ransac (include/vslam_pnp.h): a pose without a prior for each item, from points (B, S, 3) f64 seen at xy
+        (B, S, 2) f32, n (B,) i32 of them, seeds (B,) i32 / u32 bits; K: the 3 x 3 camera matrix (host); R (B, 9 or 3, 3) and T
+        (B, 3) f64 are written IN PLACE where an item is found and keep their bits elsewhere.  params: fields of vslam_pnp_params
+        over its defaults; polish: None (no polish) or a dict of vslam_resect_params fields over their defaults.  out: a dict of
+        output tensors to write into (missing ones are made, zero-filled).  Returns the dict: R, T; inlier (B, S) i32;
+        corr_points (B, S, 3) f64; corr_xy (B, S, 2) f32; corr_index (B, S) i32 (want_index); n_inliers, winner (B,) i32; counts
+        (B, hypotheses, 4) i32 (want_counts); stats (B, 4) f64 (want_stats)."""
+        import numpy as np
+        torch = self.torch
+        B, S, _ = points.shape
+        for x, dt, nm in ((points, torch.float64, "points"), (xy, torch.float32, "xy"), (n, torch.int32, "n"), (seeds, torch.int32, "seeds"),
+                          (R, torch.float64, "R"), (T, torch.float64, "T")):
+            self._dev(x, dt, nm)
+        prm = PnpParams.make(self.lib, **params)
+        shapes = dict(inlier=((B, S), torch.int32), corr_points=((B, S, 3), torch.float64), corr_xy=((B, S, 2), torch.float32),
+                      n_inliers=((B,), torch.int32), winner=((B,), torch.int32))
+        if want_index:
+            shapes.update(corr_index=((B, S), torch.int32))
+        if want_counts:
+            shapes.update(counts=((B, max(int(prm.hypotheses), 0), 4), torch.int32))
+        if want_stats:
+            shapes.update(stats=((B, 4), torch.float64))
+        o = dict(out or {})
+        for k, (shape, dt) in shapes.items():
+            if k not in o:
+                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
+            self._dev(o[k], dt, k)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        pol = None if polish is None else ResectParams.make(self.lib, **polish)
+        self._ready()
+        self._check(self.lib.vslam_pnp_ransac(
+            self.handle, _ptr(points), _ptr(xy), _ptr(n), C.c_int(B), C.c_int(S), Kh.ctypes.data_as(C.c_void_p), _ptr(seeds), C.byref(prm),
+            C.byref(pol) if pol is not None else C.c_void_p(0), _ptr(R), _ptr(T), _ptr(o["inlier"]), _ptr(o["corr_points"]), _ptr(o["corr_xy"]),
+            _ptr(o.get("corr_index")), _ptr(o["n_inliers"]), _ptr(o["winner"]), _ptr(o.get("counts")), _ptr(o.get("stats"))))
+        o.update(R=R, T=T)
+        return o
+
+    def match_points(self, points, n_points, obs_offsets, obs_desc, xy, desc, n_kp, kp_taken=None, out=None, want_indices=True,
+                     want_stats=True, **params):
+        """vslam_match_points (include/vslam_pnp.h): search_projection without a pose -- every point (B, S, 4) f32 with a valid CSR
+        row (obs_offsets (B, S + 1) i32, obs_desc (B, O, 32) u8) against every keypoint (xy (B, Kp, 2) f32, desc (B, Kp, 32) u8,
+        n_kp (B,) i32) that is not taken (kp_taken (B, Kp) i32 or None); params: fields of vslam_match_params over its defaults.
+        out and the returned dict as search_projection's."""
+        torch = self.torch
+        B, S, _ = points.shape
+        Kp, O = xy.shape[1], obs_desc.shape[1]
+        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
+                          (obs_desc, torch.uint8, "obs_desc"), (xy, torch.float32, "xy"), (desc, torch.uint8, "desc"), (n_kp, torch.int32, "n_kp"),
+                          (kp_taken, torch.int32, "kp_taken")):
+            self._dev(x, dt, nm)
+        if tuple(obs_offsets.shape) != (B, S + 1):
+            raise ValueError(f"obs_offsets has shape {tuple(obs_offsets.shape)}, not {(B, S + 1)}")
+        shapes = dict(kp_of_point=((B, S), torch.int32), dist=((B, S), torch.int32), corr_points=((B, Kp, 3), torch.float64),
+                      corr_xy=((B, Kp, 2), torch.float32), n_corr=((B,), torch.int32))
+        if want_indices:
+            shapes.update(corr_point=((B, Kp), torch.int32), corr_kp=((B, Kp), torch.int32))
+        if want_stats:
+            shapes.update(stats=((B, 4), torch.int32))
+        o = dict(out or {})
+        for k, (shape, dt) in shapes.items():
+            if k not in o:
+                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
+            self._dev(o[k], dt, k)
+        prm = MatchParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_match_points(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_desc), C.c_int(O), _ptr(xy), _ptr(desc),
+            _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken), C.c_int(B), C.byref(prm), _ptr(o["kp_of_point"]), _ptr(o["dist"]),
+            _ptr(o["corr_points"]), _ptr(o["corr_xy"]), _ptr(o.get("corr_point")), _ptr(o.get("corr_kp")), _ptr(o["n_corr"]),
+            _ptr(o.get("stats"))))
         return o
 
     def kdtree_build(self, xy, n):
@@ -1093,6 +1205,36 @@ class World:
             self.ctx.handle, self.handle, pmap.handle, _ptr(xy), _ptr(desc), _ptr(n), Kh.ctypes.data_as(C.c_void_p), C.c_int(width),
             C.c_int(height), C.byref(sprm), C.byref(rprm) if rprm is not None else C.c_void_p(0), _ptr(out["corr_point"]),
             _ptr(out["corr_kp"]), _ptr(out["n_corr"]), _ptr(out.get("stats"))))
+        return out
+
+    def relocalise(self, pmap, cur, K, seeds=None, polish={}, match=None, **params):
+        """vslam_world_relocalise (include/vslam_pnp.h): the pose of the frame `cur` (a dict of xy (tracks, kp_stride, 2) f32, desc
+        (tracks, kp_stride, 32) u8, n (tracks,) i32) of every track found from the map alone -- the last recorded pose is not
+        read --: the world's points matched to the keypoints by descriptor, P3P RANSAC over the matches, the polish (a dict of
+        vslam_resect_params fields, {} for the defaults, None for none), and for the tracks that were found the write-back of
+        search().  This world must be the one attached to `pmap`.  seeds: (tracks,) i32 bits, 1 .. tracks when None; params: fields of
+        vslam_pnp_params over its defaults; match: a dict of vslam_match_params fields.  Returns a dict of cuda tensors: found,
+        winner, n_inliers, n_corr (tracks,) i32; corr_point, corr_kp (tracks, kp_stride) i32; stats (tracks, 4) f64."""
+        import numpy as np
+        torch = self.ctx.torch
+        xy, desc, n = (self.ctx._dev(cur[k], dt, k) for k, dt in (("xy", torch.float32), ("desc", torch.uint8), ("n", torch.int32)))
+        if seeds is None:
+            seeds = torch.arange(1, self.tracks + 1, dtype=torch.int32, device=xy.device)
+        self.ctx._dev(seeds, torch.int32, "seeds")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        i32 = dict(dtype=torch.int32, device=xy.device)
+        out = dict(found=torch.zeros((self.tracks,), **i32), winner=torch.zeros((self.tracks,), **i32),
+                   n_inliers=torch.zeros((self.tracks,), **i32), corr_point=torch.zeros((self.tracks, self.kp_stride), **i32),
+                   corr_kp=torch.zeros((self.tracks, self.kp_stride), **i32), n_corr=torch.zeros((self.tracks,), **i32),
+                   stats=torch.zeros((self.tracks, 4), dtype=torch.float64, device=xy.device))
+        mprm = MatchParams.make(self.lib, **(match or {}))
+        pprm = PnpParams.make(self.lib, **params)
+        rprm = ResectParams.make(self.lib, **polish) if polish is not None else None
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_relocalise(
+            self.ctx.handle, self.handle, pmap.handle, _ptr(xy), _ptr(desc), _ptr(n), Kh.ctypes.data_as(C.c_void_p), _ptr(seeds),
+            C.byref(mprm), C.byref(pprm), C.byref(rprm) if rprm is not None else C.c_void_p(0), _ptr(out["found"]), _ptr(out["winner"]),
+            _ptr(out["n_inliers"]), _ptr(out["corr_point"]), _ptr(out["corr_kp"]), _ptr(out["n_corr"]), _ptr(out["stats"])))
         return out
 
     def set_resection(self, enable=True, **params):

@@ -342,6 +342,18 @@ int launch_search(vslam_ctx *ctx, SearchArgs a, int batch, const float *h_K) {
 
 vslam_world *vs_map_world(vslam_map *map);   // map.hip
 
+// vslam_world_search's write-back for another caller (pnp.hip, vslam_world_relocalise): frame f1 of every track whose mark[4 b + 3]
+// is a number gets (R, T) [tracks][9] / [tracks][3] written as d_Twc / d_pose and the latest carry re-expressed
+int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double *R, double *T, double *mark) {
+    WorldSearch w;
+    w.max_frames = world->max_frames; w.kp_stride = world->kp_stride; w.f1 = f1;
+    w.Twc = world->Twc; w.pose = world->pose; w.carry = world->carry; w.carry_idx = world->carry_idx;
+    w.R = R; w.T = T; w.stats = mark;
+    world_search_writeback_kernel<<<world->tracks, kST, 0, ctx->stream>>>(w, nullptr);
+    VS_HIP(ctx, hipGetLastError());
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_search_params_default(vslam_search_params *out) {

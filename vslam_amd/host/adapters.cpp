@@ -888,6 +888,18 @@ void search_projection(vslam_ctx *ctx, const float *d_points, const s32 *d_n_poi
                                            d_corr_points, d_corr_xy, d_corr_point, d_corr_kp, d_n_corr, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_search_projection: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s32 *d_n, int batch, int stride, const cv::Mat &K,
+                const unsigned int *d_seeds, f64 *d_R, f64 *d_T, s32 *d_inlier, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_index,
+                s32 *d_n_inliers, s32 *d_winner, s32 *d_counts, f64 *d_stats, const vslam_pnp_params *params,
+                const vslam_resect_params *polish) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("pnp_ransac: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_pnp_ransac(ctx, d_points, d_xy, d_n, batch, stride, k, d_seeds, params, polish, d_R, d_T, d_inlier, d_corr_points,
+                                    d_corr_xy, d_corr_index, d_n_inliers, d_winner, d_counts, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_pnp_ransac: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
