@@ -398,6 +398,28 @@ def test_match_points_batch_of_three_and_determinism(ctx):
     assert np.array_equal(got["corr_point"][0, :m], rev["corr_point"][2, :m]) and np.array_equal(got["corr_kp"][0, :m], rev["corr_kp"][2, :m])
 
 
+def test_search_and_match_in_turn_on_one_context(ctx):
+    """The search and the match share their key and proposal slots of the arena: four calls in turn on one context and stream, a
+    larger one ahead of a smaller one each way round, so that the later call finds the earlier one's keys and proposals behind its
+    own extent (300 points straddle a chunk of 256).  Each call is held bit for bit to its own reference."""
+    import search_cases as sc
+    from test_gpu_search import _case_batch, _hold, _reference, _search
+
+    def search(c):
+        b, taken = _case_batch(c)
+        ref = _reference(b, c["K"], c["width"], c["height"], taken)
+        assert ref["n_corr"][0] >= 1
+        _hold(_search(ctx, b, c["K"], c["width"], c["height"], taken), ref)
+
+    def match(c):
+        got, dims = _match(ctx, [c])
+        assert _hold_match(got, dims, [c])["n_corr"][0] >= 1
+    search(sc.random_case(1, 300, 257, 640, 480, 8.0))
+    match(pc.match_case(*MATCH_SHAPES["5x1x3"][0]))
+    match(pc.match_case(*MATCH_SHAPES["300x1-4x257"][0], **MATCH_SHAPES["300x1-4x257"][1]))
+    search(sc.random_case(8, 5, 3, 640, 480, 8.0))
+
+
 def test_match_points_refusals(ctx):
     c = pc.match_case(2, 300, (1, 4), 257, taken=True)
     b, taken = _match_batch([c])

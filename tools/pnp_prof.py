@@ -4,7 +4,7 @@ mean per launch over `--reps` calls):
   pnp     pnp_solve_kernel, pnp_count_kernel, pnp_select_kernel and the polish (resect_poses_kernel) at `--items` items of
           `--corr` correspondences, `--hypotheses` hypotheses, half of the keypoints replaced by random pixels
           (tests/ref_pnp.planted, one scene broadcast to every item with a seed of its own);
-  match   match_propose_kernel and match_resolve_kernel at `--items` items of `--points` points with 1 to 3 observations against
+  match   match_propose_kernel and corr_resolve_kernel at `--items` items of `--points` points with 1 to 3 observations against
           `--keypoints` keypoints (tests/pnp_cases.match_case).
 No target time is set; the numbers are a record to measure later work against.
 
@@ -67,7 +67,7 @@ def child(a):
     def match():
         mout.update(ctx.match_points(m["points"], m["n_points"], m["offsets"], m["obs_desc"], m["xy"], m["desc"], m["n_kp"], out=mout or None))
         return mout
-    o, kern = timed(match, ("match_propose", "match_resolve"))
+    o, kern = timed(match, ("match_propose", "corr_resolve"))
     result["match"] = dict(items=B, points=a.points, observations="1-3", keypoints=a.keypoints, stats=o["stats"][0].cpu().numpy().tolist(), kernels=kern)
     ctx.close()
     print("PNP_PROF " + json.dumps(result))

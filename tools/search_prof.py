@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""vslam_prof_* readings of the search by projection (include/vslam_search.h): search_propose_kernel and search_resolve_kernel at
+"""vslam_prof_* readings of the search by projection (include/vslam_search.h): search_propose_kernel and corr_resolve_kernel at
 `--items` items of `--keypoints` keypoints in a 1280 x 720 frame, `--points` points per item (4000 and 16000 by default) with 1 to
 5 observations each, radius 8, from a pose a few pixels off (tests/search_cases.random_case's construction: keypoints scattered
 on the projections, descriptors from a pool so that ties, ratio rejections and contests occur).  Per shape: a warm-up call, then
@@ -24,6 +24,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, RADIUS = 1280, 720, 8.0
+KERNELS = ("search_propose", "corr_resolve")
 
 
 def child(a):
@@ -69,8 +70,8 @@ def child(a):
                 search(dd, radius)
             ctx.synchronize()
             rep = ctx.prof_report()
-            readings[name] = dict(stats=stats, mean_ms_per_launch={k: ms / max(cnt, 1) for k, (ms, cnt) in rep.items() if k.startswith("search_")},
-                                  launches={k: cnt for k, (ms, cnt) in rep.items() if k.startswith("search_")})
+            readings[name] = dict(stats=stats, mean_ms_per_launch={k: ms / max(cnt, 1) for k, (ms, cnt) in rep.items() if k.startswith(KERNELS)},
+                                  launches={k: cnt for k, (ms, cnt) in rep.items() if k.startswith(KERNELS)})
         # for scale: the reference-exact association's candidate kernel on the same points and keypoints
         ctx.prof_enable(False)
         nodes = ctx.kdtree_build(d["xy"], d["n_kp"])

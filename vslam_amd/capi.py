@@ -49,103 +49,61 @@ RESECT_SYMBOLS = [
 ]
 
 
-class ResectParams(C.Structure):   # vslam_resect_params
-    _fields_ = [("max_iterations", C.c_int32), ("rounds", C.c_int32), ("min_links", C.c_int32), ("huber_px", C.c_double),
-                ("gate_px", C.c_double)]
+class _Params(C.Structure):
+    """A parameter struct of the C ABI: a subclass states its _fields_ and the struct's name, `_struct`, whose <_struct>_default
+    fills it."""
 
     @classmethod
     def make(cls, lib, **fields):
-        """vslam_resect_params_default with `fields` written over it"""
+        """<_struct>_default with `fields` written over it"""
         p = cls()
-        rc = lib.vslam_resect_params_default(C.byref(p))
+        rc = getattr(lib, cls._struct + "_default")(C.byref(p))
         if rc != OK:
-            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_resect_params_default")
+            raise VslamError(f"{ERRORS.get(rc, rc)}: {cls._struct}_default")
         for k, v in fields.items():
             if k not in dict(cls._fields_):
-                raise TypeError(f"vslam_resect_params has no field {k!r}")
+                raise TypeError(f"{cls._struct} has no field {k!r}")
             setattr(p, k, v)
         return p
+
+
+class ResectParams(_Params):
+    _struct = "vslam_resect_params"
+    _fields_ = [("max_iterations", C.c_int32), ("rounds", C.c_int32), ("min_links", C.c_int32), ("huber_px", C.c_double),
+                ("gate_px", C.c_double)]
 
 
 # every symbol include/vslam_adjust.h declares (a header of its own; tests/test_gpu_adjust.py checks it)
 ADJUST_SYMBOLS = ["vslam_adjust_params_default", "vslam_adjust_windows", "vslam_world_adjust"]
 
 
-class AdjustParams(C.Structure):   # vslam_adjust_params
+class AdjustParams(_Params):
+    _struct = "vslam_adjust_params"
     _fields_ = [("max_iterations", C.c_int32), ("rounds", C.c_int32), ("min_obs", C.c_int32), ("n_fixed", C.c_int32),
                 ("huber_px", C.c_double), ("gate_px", C.c_double)]
-
-    @classmethod
-    def make(cls, lib, **fields):
-        """vslam_adjust_params_default with `fields` written over it"""
-        p = cls()
-        rc = lib.vslam_adjust_params_default(C.byref(p))
-        if rc != OK:
-            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_adjust_params_default")
-        for k, v in fields.items():
-            if k not in dict(cls._fields_):
-                raise TypeError(f"vslam_adjust_params has no field {k!r}")
-            setattr(p, k, v)
-        return p
 
 
 # every symbol include/vslam_search.h declares (a header of its own; tests/test_gpu_search.py checks it)
 SEARCH_SYMBOLS = ["vslam_search_params_default", "vslam_search_projection", "vslam_map_observation_descriptors", "vslam_world_search"]
 
 
-class SearchParams(C.Structure):   # vslam_search_params
+class SearchParams(_Params):
+    _struct = "vslam_search_params"
     _fields_ = [("radius_px", C.c_double), ("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
-
-    @classmethod
-    def make(cls, lib, **fields):
-        """vslam_search_params_default with `fields` written over it"""
-        p = cls()
-        rc = lib.vslam_search_params_default(C.byref(p))
-        if rc != OK:
-            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_search_params_default")
-        for k, v in fields.items():
-            if k not in dict(cls._fields_):
-                raise TypeError(f"vslam_search_params has no field {k!r}")
-            setattr(p, k, v)
-        return p
 
 
 # every symbol include/vslam_pnp.h declares (a header of its own; tests/test_pnp_lds.py checks it)
 PNP_SYMBOLS = ["vslam_pnp_params_default", "vslam_pnp_ransac", "vslam_match_params_default", "vslam_match_points", "vslam_world_relocalise"]
 
 
-class PnpParams(C.Structure):   # vslam_pnp_params
+class PnpParams(_Params):
+    _struct = "vslam_pnp_params"
     _fields_ = [("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("inlier_px", C.c_double)]
 
-    @classmethod
-    def make(cls, lib, **fields):
-        """vslam_pnp_params_default with `fields` written over it"""
-        p = cls()
-        rc = lib.vslam_pnp_params_default(C.byref(p))
-        if rc != OK:
-            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_pnp_params_default")
-        for k, v in fields.items():
-            if k not in dict(cls._fields_):
-                raise TypeError(f"vslam_pnp_params has no field {k!r}")
-            setattr(p, k, v)
-        return p
 
-
-class MatchParams(C.Structure):   # vslam_match_params
+class MatchParams(_Params):
+    _struct = "vslam_match_params"
     _fields_ = [("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
-
-    @classmethod
-    def make(cls, lib, **fields):
-        """vslam_match_params_default with `fields` written over it"""
-        p = cls()
-        rc = lib.vslam_match_params_default(C.byref(p))
-        if rc != OK:
-            raise VslamError(f"{ERRORS.get(rc, rc)}: vslam_match_params_default")
-        for k, v in fields.items():
-            if k not in dict(cls._fields_):
-                raise TypeError(f"vslam_match_params has no field {k!r}")
-            setattr(p, k, v)
-        return p
 
 
 class ExtractParams(C.Structure):
@@ -538,21 +496,25 @@ class Context:
                                                   Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
         return R, T, points, stats
 
-    def search_projection(self, points, n_points, obs_offsets, obs_desc, R, T, K, width, height, xy, desc, n_kp, kp_taken=None,
-                          out=None, want_indices=True, want_stats=True, **params):
-        """vslam_search_projection (include/vslam_search.h): each item's points (B, S, 4) f32, n_points (B,) i32 of them, with their
-        observation descriptors in CSR (obs_offsets (B, S + 1) i32, obs_desc (B, O, 32) u8), projected with R (B, 9) / T (B, 3) f64
-        and K (the 3 x 3 camera matrix, host) into a width x height frame with keypoints xy (B, Kp, 2) f32, desc (B, Kp, 32) u8, n_kp
-        (B,) i32; kp_taken (B, Kp) i32 or None; params: fields of vslam_search_params over its defaults.  out: a dict of output
-        tensors to write into (missing ones are made, zero-filled).  Returns the dict: kp_of_point, dist (B, S) i32; corr_points
-        (B, Kp, 3) f64; corr_xy (B, Kp, 2) f32; corr_point, corr_kp (B, Kp) i32 (want_indices); n_corr (B,) i32; stats (B, 4) i32
-        (want_stats) -- the layout resect_poses reads."""
-        import numpy as np
+    def _outputs(self, out, shapes, device):
+        """`out` (a dict of output tensors or None) as a new dict with the missing tensors of `shapes` (name -> (shape, dtype)) made,
+        zero-filled, and every one of them checked"""
+        o = dict(out or {})
+        for k, (shape, dt) in shapes.items():
+            if k not in o:
+                o[k] = self.torch.zeros(shape, dtype=dt, device=device)
+            self._dev(o[k], dt, k)
+        return o
+
+    def _correspond(self, call, params_cls, params, pose, pose_args, points, n_points, obs_offsets, obs_desc, xy, desc, n_kp, kp_taken,
+                    out, want_indices, want_stats):
+        """search_projection and match_points: `call` is the library's entry point, params the fields over params_cls' defaults; the
+        projection alone has pose, its (name, f64 tensor) pairs, and pose_args, its C arguments between them and d_xy"""
         torch = self.torch
         B, S, _ = points.shape
         Kp, O = xy.shape[1], obs_desc.shape[1]
         for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
-                          (obs_desc, torch.uint8, "obs_desc"), (R, torch.float64, "R"), (T, torch.float64, "T"), (xy, torch.float32, "xy"),
+                          (obs_desc, torch.uint8, "obs_desc"), *((x, torch.float64, nm) for nm, x in pose), (xy, torch.float32, "xy"),
                           (desc, torch.uint8, "desc"), (n_kp, torch.int32, "n_kp"), (kp_taken, torch.int32, "kp_taken")):
             self._dev(x, dt, nm)
         if tuple(obs_offsets.shape) != (B, S + 1):
@@ -563,20 +525,30 @@ class Context:
             shapes.update(corr_point=((B, Kp), torch.int32), corr_kp=((B, Kp), torch.int32))
         if want_stats:
             shapes.update(stats=((B, 4), torch.int32))
-        o = dict(out or {})
-        for k, (shape, dt) in shapes.items():
-            if k not in o:
-                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
-            self._dev(o[k], dt, k)
-        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
-        prm = SearchParams.make(self.lib, **params)
+        o = self._outputs(out, shapes, points.device)
+        prm = params_cls.make(self.lib, **params)
         self._ready()
-        self._check(self.lib.vslam_search_projection(
-            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_desc), C.c_int(O), _ptr(R), _ptr(T),
-            Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height), _ptr(xy), _ptr(desc), _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken),
-            C.c_int(B), C.byref(prm), _ptr(o["kp_of_point"]), _ptr(o["dist"]), _ptr(o["corr_points"]), _ptr(o["corr_xy"]),
-            _ptr(o.get("corr_point")), _ptr(o.get("corr_kp")), _ptr(o["n_corr"]), _ptr(o.get("stats"))))
+        self._check(call(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_desc), C.c_int(O),
+            *(_ptr(x) for _, x in pose), *pose_args, _ptr(xy), _ptr(desc), _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken), C.c_int(B), C.byref(prm),
+            _ptr(o["kp_of_point"]), _ptr(o["dist"]), _ptr(o["corr_points"]), _ptr(o["corr_xy"]), _ptr(o.get("corr_point")),
+            _ptr(o.get("corr_kp")), _ptr(o["n_corr"]), _ptr(o.get("stats"))))
         return o
+
+    def search_projection(self, points, n_points, obs_offsets, obs_desc, R, T, K, width, height, xy, desc, n_kp, kp_taken=None,
+                          out=None, want_indices=True, want_stats=True, **params):
+        """vslam_search_projection (include/vslam_search.h): each item's points (B, S, 4) f32, n_points (B,) i32 of them, with their
+        observation descriptors in CSR (obs_offsets (B, S + 1) i32, obs_desc (B, O, 32) u8), projected with R (B, 9) / T (B, 3) f64
+        and K (the 3 x 3 camera matrix, host) into a width x height frame with keypoints xy (B, Kp, 2) f32, desc (B, Kp, 32) u8, n_kp
+        (B,) i32; kp_taken (B, Kp) i32 or None; params: fields of vslam_search_params over its defaults.  out: a dict of output
+        tensors to write into (missing ones are made, zero-filled).  Returns the dict: kp_of_point, dist (B, S) i32; corr_points
+        (B, Kp, 3) f64; corr_xy (B, Kp, 2) f32; corr_point, corr_kp (B, Kp) i32 (want_indices); n_corr (B,) i32; stats (B, 4) i32
+        (want_stats) -- the layout resect_poses reads."""
+        import numpy as np
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        return self._correspond(self.lib.vslam_search_projection, SearchParams, params, (("R", R), ("T", T)),
+                                (Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height)), points, n_points,
+                                obs_offsets, obs_desc, xy, desc, n_kp, kp_taken, out, want_indices, want_stats)
 
     def pnp_ransac(self, points, xy, n, K, seeds, R, T, polish=None, out=None, want_index=True, want_counts=False, want_stats=True,
                    **params):
@@ -602,11 +574,7 @@ class Context:
             shapes.update(counts=((B, max(int(prm.hypotheses), 0), 4), torch.int32))
         if want_stats:
             shapes.update(stats=((B, 4), torch.float64))
-        o = dict(out or {})
-        for k, (shape, dt) in shapes.items():
-            if k not in o:
-                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
-            self._dev(o[k], dt, k)
+        o = self._outputs(out, shapes, points.device)
         Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
         pol = None if polish is None else ResectParams.make(self.lib, **polish)
         self._ready()
@@ -623,34 +591,8 @@ class Context:
         row (obs_offsets (B, S + 1) i32, obs_desc (B, O, 32) u8) against every keypoint (xy (B, Kp, 2) f32, desc (B, Kp, 32) u8,
         n_kp (B,) i32) that is not taken (kp_taken (B, Kp) i32 or None); params: fields of vslam_match_params over its defaults.
         out and the returned dict as search_projection's."""
-        torch = self.torch
-        B, S, _ = points.shape
-        Kp, O = xy.shape[1], obs_desc.shape[1]
-        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
-                          (obs_desc, torch.uint8, "obs_desc"), (xy, torch.float32, "xy"), (desc, torch.uint8, "desc"), (n_kp, torch.int32, "n_kp"),
-                          (kp_taken, torch.int32, "kp_taken")):
-            self._dev(x, dt, nm)
-        if tuple(obs_offsets.shape) != (B, S + 1):
-            raise ValueError(f"obs_offsets has shape {tuple(obs_offsets.shape)}, not {(B, S + 1)}")
-        shapes = dict(kp_of_point=((B, S), torch.int32), dist=((B, S), torch.int32), corr_points=((B, Kp, 3), torch.float64),
-                      corr_xy=((B, Kp, 2), torch.float32), n_corr=((B,), torch.int32))
-        if want_indices:
-            shapes.update(corr_point=((B, Kp), torch.int32), corr_kp=((B, Kp), torch.int32))
-        if want_stats:
-            shapes.update(stats=((B, 4), torch.int32))
-        o = dict(out or {})
-        for k, (shape, dt) in shapes.items():
-            if k not in o:
-                o[k] = torch.zeros(shape, dtype=dt, device=points.device)
-            self._dev(o[k], dt, k)
-        prm = MatchParams.make(self.lib, **params)
-        self._ready()
-        self._check(self.lib.vslam_match_points(
-            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_desc), C.c_int(O), _ptr(xy), _ptr(desc),
-            _ptr(n_kp), C.c_int(Kp), _ptr(kp_taken), C.c_int(B), C.byref(prm), _ptr(o["kp_of_point"]), _ptr(o["dist"]),
-            _ptr(o["corr_points"]), _ptr(o["corr_xy"]), _ptr(o.get("corr_point")), _ptr(o.get("corr_kp")), _ptr(o["n_corr"]),
-            _ptr(o.get("stats"))))
-        return o
+        return self._correspond(self.lib.vslam_match_points, MatchParams, params, (), (), points, n_points, obs_offsets, obs_desc, xy, desc,
+                                n_kp, kp_taken, out, want_indices, want_stats)
 
     def kdtree_build(self, xy, n):
         torch = self.torch

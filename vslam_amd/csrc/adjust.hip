@@ -271,8 +271,6 @@ __global__ __launch_bounds__(kAT) void world_adjust_scatter_kernel(WorldAdjust g
 }
 }  // namespace
 
-vslam_world *vs_map_world(vslam_map *map);   // map.hip
-
 extern "C" {
 
 int vslam_adjust_params_default(vslam_adjust_params *out) {
@@ -316,12 +314,10 @@ int vslam_world_adjust(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const
                        int window, const vslam_adjust_params *params, double *d_stats) {
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, world && map && d_xy && h_K, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, world->ctx == ctx && vs_map_world(map) == world && world->world_points, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, window >= 2 && window <= VSLAM_ADJUST_MAX_CAMS, VSLAM_ERR_INVALID);
     vslam_map_arrays m;
-    int rc = vslam_map_view(map, &m);
+    int rc = vs_world_map_view(ctx, world, map, &m);
     if (rc != VSLAM_OK) return rc;
-    VS_REQUIRE(ctx, m.frames == world->frames && xy_frames >= m.frames, VSLAM_ERR_INVALID);
+    VS_REQUIRE(ctx, window >= 2 && window <= VSLAM_ADJUST_MAX_CAMS && xy_frames >= m.frames, VSLAM_ERR_INVALID);
     VS_ALIGNED(ctx, d_xy, 8);
     VS_ALIGNED(ctx, d_stats, 8);
     vslam_adjust_params p;

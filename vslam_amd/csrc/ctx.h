@@ -379,3 +379,29 @@ int vs_launch_world_resect(vslam_ctx *ctx, vslam_world *w, int fid, const int32_
                            const float *h_K);
 int vs_world_resect_reset(vslam_ctx *ctx, vslam_world *w);
 bool vs_resect_params_ok(const vslam_resect_params &p);
+
+// ---- a world attached to a map, for the calls that read both (adjust.hip, search.hip, pnp.hip) ----
+vslam_world *vs_map_world(vslam_map *map);   // map.hip: the world the map has attached, or null
+// `world` is this context's, the one attached to `map`, and lifted
+static inline bool vs_world_of_map(vslam_ctx *ctx, vslam_world *world, vslam_map *map) {
+    return world->ctx == ctx && vs_map_world(map) == world && world->world_points;
+}
+// search.hip: vs_world_of_map, and the world has as many frames as the map, whose view is *m
+int vs_world_map_view(vslam_ctx *ctx, vslam_world *world, vslam_map *map, vslam_map_arrays *m);
+// What vslam_world_search and vslam_world_relocalise open with (search.hip): vs_world_map_view, the alignment of the current frame's
+// arrays, and the arena workspace of both calls, with the map's CSR and its observation descriptors queued into it.
+struct VsWorldCorr {
+    vslam_map_arrays m;
+    int32_t *off, *kp_of_point, *dist;   // [tracks][map_capacity + 1], [tracks][map_capacity] twice
+    uint8_t *obs_desc;                   // [tracks][obs_capacity][32]
+    double *R, *T, *mark;                // [tracks][9], [tracks][3], [tracks][4]: a pose and what vs_world_search_writeback reads
+    double *corr_points;                 // [tracks][kp_stride][3]
+    float *corr_xy;                      // [tracks][kp_stride][2]
+};
+int vs_world_corr_begin(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const float *d_xy_cur, const uint8_t *d_desc_cur,
+                        const double *d_stats, VsWorldCorr *c);
+// vslam_world_search's write-back (search.hip): frame f1 of every track whose mark[4 b + 3] is a number gets (R, T) [tracks][9] /
+// [tracks][3] written as d_Twc / d_pose and the latest carry re-expressed
+int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double *R, double *T, double *mark);
+struct vslam_match_params;   // include/vslam_pnp.h
+bool vs_match_params_ok(const vslam_match_params &p);   // search.hip

@@ -15,6 +15,7 @@
 // that runs out of map or observation slots anywhere in the step is left exactly as it was.
 #include <algorithm>
 
+#include "block_scan.h"
 #include "ctx.h"
 #include "../../include/vslam_search.h"
 
@@ -58,29 +59,6 @@ struct vslam_map {
 namespace {
 
 constexpr int kMT = 256;   // threads of the per-track kernels: one workgroup per track
-
-// exclusive prefix of `v` over the workgroup (kMT threads, wave64); every thread calls it.  lds: kMT / 64 words.
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kMT / 64; w++) {
-        const int s = lds[w];
-        if (w < wv) base += s;
-        total += s;
-    }
-    __syncthreads();
-    return base + inc - v;
-}
 
 __device__ __forceinline__ void copy_desc(uint8_t *dst, const uint8_t *src) {   // 32-byte rows, 16-byte aligned
     const uint4 a = reinterpret_cast<const uint4 *>(src)[0], b = reinterpret_cast<const uint4 *>(src)[1];
@@ -201,7 +179,7 @@ __global__ __launch_bounds__(kMT) void map_propagate_kernel(MapDev m, int fid, c
         }
     }
     int total;
-    block_excl_scan(mine, lds, total);
+    vs_block_excl_scan<kMT>(mine, lds, total);
     const int base = m.n_obs[b];
     if (base + total > m.obs_capacity) {   // nothing partial: the whole step of this track is dropped
         if (tid == 0) {
@@ -239,7 +217,7 @@ __global__ __launch_bounds__(kMT) void map_propagate_kernel(MapDev m, int fid, c
         const int k = k0 + tid;
         const bool push = k < n && krank[k] >= 0;
         int chunk;
-        const int pos = run + block_excl_scan(push ? 1 : 0, lds, chunk);
+        const int pos = run + vs_block_excl_scan<kMT>(push ? 1 : 0, lds, chunk);
         run += chunk;
         if (push) {
             const int2 mt = M[k];
@@ -271,7 +249,7 @@ __global__ __launch_bounds__(kMT) void map_offsets_kernel(const int32_t *__restr
         const int i = i0 + tid;
         const int v = i < n ? c[i] : 0;
         int chunk;
-        const int ex = block_excl_scan(v, lds, chunk);
+        const int ex = vs_block_excl_scan<kMT>(v, lds, chunk);
         if (i < n) o[i] = run + ex;
         run += chunk;
     }
@@ -316,7 +294,7 @@ __global__ __launch_bounds__(kMT) void map_assoc_push_kernel(MapDev m, int fid, 
     int mine = 0;
     for (int i = tid; i < n; i += kMT) mine += (claim[i] >= 0 && claim[i] < K) ? 1 : 0;
     int total;
-    block_excl_scan(mine, lds, total);
+    vs_block_excl_scan<kMT>(mine, lds, total);
     const int base = m.n_obs[b] + m.pend[b];
     if (base + total > m.obs_capacity) {
         if (tid == 0) m.fail[b] = 1;
@@ -328,7 +306,7 @@ __global__ __launch_bounds__(kMT) void map_assoc_push_kernel(MapDev m, int fid, 
         const int kp = i < n ? claim[i] : -1;
         const bool push = kp >= 0 && kp < K;
         int chunk;
-        const int pos = run + block_excl_scan(push ? 1 : 0, lds, chunk);
+        const int pos = run + vs_block_excl_scan<kMT>(push ? 1 : 0, lds, chunk);
         run += chunk;
         if (push) {
             const size_t e = (size_t)b * m.obs_capacity + pos;

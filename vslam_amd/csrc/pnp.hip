@@ -9,15 +9,14 @@
 //           no bank conflict).  No atomics, no per-correspondence global traffic.
 //   select  one workgroup per item: the maximum of the integer keys, then the winner's mask again (the same function on the same
 //           operands: the same bits), compacted in ascending order with a ballot scan.
-// The polish is vslam_resect_poses' own launch on the compacted rows.  Further down: vslam_match_points (world points to keypoints
-// by descriptor alone) and vslam_world_relocalise, which joins the two on a world attached to a map.
+// The polish is vslam_resect_poses' own launch on the compacted rows.  Further down: vslam_world_relocalise, which joins
+// vslam_match_points (search.hip: world points to keypoints by descriptor alone) and this on a world attached to a map.
 #include <cmath>
 
+#include "block_scan.h"
 #include "ctx.h"
 #include "pnp_math.h"
-#include "search_math.h"
 #include "../../include/vslam_pnp.h"
-#include "../../include/vslam_search.h"
 
 #pragma clang fp contract(off)
 
@@ -150,24 +149,6 @@ __global__ __launch_bounds__(kPT) void pnp_count_kernel(PnpArgs a, VsK Kc) {
     if (a.counts_out) a.counts_out[pose] = v;
 }
 
-// exclusive prefix of a flag over the workgroup by ballots; every lane calls it.  lds: kPT / 64 words.
-__device__ __forceinline__ int block_flag_scan(bool f, int *lds, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) lds[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kPT / 64; w++) {
-        const int c = lds[w];
-        before += w < wave ? c : 0;
-        total += c;
-    }
-    __syncthreads();
-    return before + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
 __global__ __launch_bounds__(kPT) void pnp_select_kernel(PnpArgs a, VsK Kc) {
     __shared__ uint32_t best;
     __shared__ int wave_n[kPT / 64];
@@ -226,7 +207,7 @@ __global__ __launch_bounds__(kPT) void pnp_select_kernel(PnpArgs a, VsK Kc) {
         }
         if (i < a.stride) inl[i] = in ? 1 : 0;
         int total;
-        const int slot = running + block_flag_scan(in, wave_n, total);
+        const int slot = running + vs_block_flag_scan<kPT>(in, wave_n, total);
         if (in) {
             cp[3 * (size_t)slot] = p[0];
             cp[3 * (size_t)slot + 1] = p[1];
@@ -236,196 +217,6 @@ __global__ __launch_bounds__(kPT) void pnp_select_kernel(PnpArgs a, VsK Kc) {
         }
         running += total;
     }
-}
-
-// ---- vslam_match_points: every point against every keypoint.  Grid (ceil(pt_stride / 256), batch), one lane per point with up to
-// four of its observation descriptors in registers (further ones are read again per keypoint); the item's keypoint descriptors
-// pass through LDS in tiles of 1024 (32 KB: VSLAM_MAX_KP x 32 B would not fit), and every lane reads the same row of the tile, a
-// broadcast.  The choice, the proposal rule and the keys are search_math.h's; the resolution is search.hip's, over these
-// proposals.
-constexpr int kMTile = 1024;     // keypoints per LDS tile
-constexpr int kMObs = 4;         // observation descriptors a lane keeps in registers
-constexpr int kPropPart = 1 << 16, kPropCandidate = 1 << 17;   // beside d0 (<= 256) in a proposal's second word
-
-struct MatchArgs {
-    const float4 *points;
-    const int32_t *n_points;
-    int pt_stride;
-    const int32_t *obs_offsets;
-    const uint8_t *obs_desc;
-    int obs_stride;
-    const float2 *xy;
-    const uint8_t *desc;
-    const int32_t *n_kp;
-    int kp_stride;
-    const int32_t *taken;
-    vs_search::SsParams prm;
-    unsigned long long *keys;   // [batch][kp_stride], all ones ahead of the proposals
-    int2 *prop;                 // [batch][pt_stride]: (k0 or -1, d0 | flags)
-    int32_t *kp_of_point, *dist;
-    double *corr_points;
-    float2 *corr_xy;
-    int32_t *corr_point, *corr_kp, *n_corr, *stats;
-};
-
-__device__ __forceinline__ void load_desc(const uint8_t *row, uint32_t (&w)[8]) {   // a 32-byte row, 16-byte aligned
-    const uint4 a = reinterpret_cast<const uint4 *>(row)[0], b = reinterpret_cast<const uint4 *>(row)[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
-__global__ __launch_bounds__(kPT) void match_propose_kernel(MatchArgs a) {
-    using namespace vs_search;
-    __shared__ uint4 tile[2 * kMTile];
-    __shared__ uint8_t cand[kMTile];
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int n = min(max(a.n_points[b], 0), a.pt_stride);
-    if (blockIdx.x * kPT >= n) return;   // the whole workgroup: the resolution writes the rows from n on
-    const int n_kp = min(max(a.n_kp[b], 0), a.kp_stride);
-    const int32_t *taken = a.taken ? a.taken + (size_t)b * a.kp_stride : nullptr;
-    const int32_t *OO = a.obs_offsets + (size_t)b * (a.pt_stride + 1);
-    const uint8_t *OD = a.obs_desc + (size_t)b * a.obs_stride * VSLAM_DESC_BYTES;
-    const uint4 *D = reinterpret_cast<const uint4 *>(a.desc + (size_t)b * a.kp_stride * VSLAM_DESC_BYTES);
-    const int i = blockIdx.x * kPT + tid;
-    bool part = false;
-    int o0 = 0, o1 = 0;
-    if (i < n) {
-        const float4 P = a.points[(size_t)b * a.pt_stride + i];
-        o0 = OO[i];
-        o1 = OO[i + 1];
-        part = o0 >= 0 && o0 < o1 && o1 <= a.obs_stride && isfinite(P.x) && isfinite(P.y) && isfinite(P.z);
-    }
-    const int cnt = part ? o1 - o0 : 0;
-    uint32_t obs[kMObs][8];
-#pragma unroll
-    for (int q = 0; q < kMObs; q++) {
-        if (q < cnt) {
-            load_desc(OD + (size_t)(o0 + q) * VSLAM_DESC_BYTES, obs[q]);
-        } else {
-#pragma unroll
-            for (int w = 0; w < 8; w++) obs[q][w] = 0u;
-        }
-    }
-    SsBest best;
-    bool any = false;
-    for (int base = 0; base < n_kp; base += kMTile) {
-        const int m = min(kMTile, n_kp - base);
-        for (int j = tid; j < 2 * m; j += kPT) tile[j] = D[2 * (size_t)base + j];
-        for (int j = tid; j < m; j += kPT) cand[j] = (taken && taken[base + j] >= 0) ? 0 : 1;
-        __syncthreads();
-        if (part) {
-            for (int j = 0; j < m; j++) {
-                if (!cand[j]) continue;   // the same in every lane
-                any = true;
-                const uint4 lo = tile[2 * j], hi = tile[2 * j + 1];
-                const uint32_t dk[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                uint32_t d = kSsNone;
-#pragma unroll
-                for (int q = 0; q < kMObs; q++) {
-                    if (q < cnt) {
-                        const uint32_t cur = ss_ham256(dk, obs[q]);
-                        d = cur < d ? cur : d;
-                    }
-                }
-                for (int o = o0 + kMObs; o < o1; o++) {
-                    uint32_t dobs[8];
-                    load_desc(OD + (size_t)o * VSLAM_DESC_BYTES, dobs);
-                    const uint32_t cur = ss_ham256(dk, dobs);
-                    d = cur < d ? cur : d;
-                }
-                ss_offer(best, d, (uint32_t)(base + j));
-            }
-        }
-        __syncthreads();
-    }
-    if (i >= n) return;
-    const bool proposes = part && ss_proposes(best, a.prm);
-    int2 pr;
-    pr.x = proposes ? (int)best.k0 : -1;
-    pr.y = (proposes ? (int)best.d0 : 0) | (part ? kPropPart : 0) | (any ? kPropCandidate : 0);
-    a.prop[(size_t)b * a.pt_stride + i] = pr;
-    if (proposes) atomicMin(&a.keys[(size_t)b * a.kp_stride + best.k0], ss_key(best.d0, (uint32_t)i));
-}
-
-// one workgroup per item: a point has found its keypoint iff the key there is its own; ordered compaction in chunks of 256 points
-__global__ __launch_bounds__(kPT) void match_resolve_kernel(MatchArgs a) {
-    using namespace vs_search;
-    __shared__ int scan_lds[kPT / 64];
-    __shared__ int counts[3];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = min(max(a.n_points[b], 0), a.pt_stride);
-    if (tid < 3) counts[tid] = 0;
-    __syncthreads();
-    const unsigned long long *keys = a.keys + (size_t)b * a.kp_stride;
-    const float2 *XY = a.xy + (size_t)b * a.kp_stride;
-    int run = 0, part = 0, with_candidate = 0, proposing = 0;
-    for (int base = 0; base < a.pt_stride; base += kPT) {   // ascending chunks: the compacted order is the points' order
-        const int i = base + tid;
-        int k0 = -1, d0 = -1;
-        bool found = false;
-        if (i < n) {
-            const int2 pr = a.prop[(size_t)b * a.pt_stride + i];
-            part += (pr.y & kPropPart) ? 1 : 0;
-            with_candidate += (pr.y & kPropCandidate) ? 1 : 0;
-            if (pr.x >= 0) {
-                proposing++;
-                k0 = pr.x;
-                d0 = pr.y & 0xFFFF;
-                found = keys[k0] == ss_key((uint32_t)d0, (uint32_t)i);
-            }
-        }
-        int chunk;
-        const int pos = run + block_flag_scan(found, scan_lds, chunk);
-        if (i < a.pt_stride) {
-            a.kp_of_point[(size_t)b * a.pt_stride + i] = found ? k0 : -1;
-            a.dist[(size_t)b * a.pt_stride + i] = found ? d0 : -1;
-        }
-        if (found) {   // one point per keypoint at the most, so pos < n_kp <= kp_stride
-            const size_t slot = (size_t)b * a.kp_stride + pos;
-            const float4 P = a.points[(size_t)b * a.pt_stride + i];
-            a.corr_points[3 * slot] = (double)P.x;
-            a.corr_points[3 * slot + 1] = (double)P.y;
-            a.corr_points[3 * slot + 2] = (double)P.z;
-            a.corr_xy[slot] = XY[k0];
-            if (a.corr_point) a.corr_point[slot] = i;
-            if (a.corr_kp) a.corr_kp[slot] = k0;
-        }
-        run += chunk;
-    }
-    if (tid == 0) a.n_corr[b] = run;
-    if (!a.stats) return;
-    atomicAdd(&counts[0], part);
-    atomicAdd(&counts[1], with_candidate);
-    atomicAdd(&counts[2], proposing);
-    __syncthreads();
-    if (tid < 3) a.stats[(size_t)b * 4 + tid] = counts[tid];
-    if (tid == 3) a.stats[(size_t)b * 4 + 3] = run;
-}
-
-// the fill of the keys and the two launches; everything has been checked
-int launch_match(vslam_ctx *ctx, MatchArgs a, int batch) {
-    int rc;
-    void *ptr = nullptr;
-    if ((rc = vs_arena_get(ctx, "match_keys", sizeof(unsigned long long) * (size_t)batch * a.kp_stride, &ptr))) return rc;
-    a.keys = static_cast<unsigned long long *>(ptr);
-    if ((rc = vs_arena_get(ctx, "match_prop", sizeof(int2) * (size_t)batch * a.pt_stride, &ptr))) return rc;
-    a.prop = static_cast<int2 *>(ptr);
-    VS_HIP(ctx, hipMemsetAsync(a.keys, 0xFF, sizeof(unsigned long long) * (size_t)batch * a.kp_stride, ctx->stream));
-    {
-        VsProfScope ps(ctx, "match_propose_kernel");
-        match_propose_kernel<<<dim3(vs_div_up(a.pt_stride, kPT), batch), kPT, 0, ctx->stream>>>(a);
-    }
-    VS_HIP(ctx, hipGetLastError());
-    {
-        VsProfScope ps(ctx, "match_resolve_kernel");
-        match_resolve_kernel<<<batch, kPT, 0, ctx->stream>>>(a);
-    }
-    VS_HIP(ctx, hipGetLastError());
-    return VSLAM_OK;
-}
-
-bool match_params_ok(const vslam_match_params &p) {
-    return p.dist_threshold >= 1 && p.dist_threshold <= 257 && p.ratio10 >= 0 && p.ratio10 <= 10;
 }
 
 // ---- vslam_world_relocalise: the tracks that were found, as the mark vs_world_search_writeback reads (a number in [3]), and d_found
@@ -443,9 +234,6 @@ bool params_ok(const vslam_pnp_params &p) {
            p.inlier_px > 0.0;
 }
 }  // namespace
-
-vslam_world *vs_map_world(vslam_map *map);                                                                                   // map.hip
-int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double *R, double *T, double *mark);   // search.hip
 
 extern "C" {
 
@@ -507,45 +295,6 @@ int vslam_pnp_ransac(vslam_ctx *ctx, const double *d_points, const float *d_xy, 
     return vslam_resect_poses(ctx, d_corr_points, d_corr_xy, d_n_inliers, batch, stride, h_K, polish, d_R, d_T, d_stats);
 }
 
-int vslam_match_params_default(vslam_match_params *out) {
-    if (!out) return VSLAM_ERR_INVALID;
-    out->dist_threshold = 64; out->ratio10 = 8;
-    return VSLAM_OK;
-}
-
-int vslam_match_points(vslam_ctx *ctx, const float *d_points, const int32_t *d_n_points, int pt_stride, const int32_t *d_obs_offsets,
-                       const uint8_t *d_obs_desc, int obs_stride, const float *d_xy, const uint8_t *d_desc, const int32_t *d_n_kp,
-                       int kp_stride, const int32_t *d_kp_taken, int batch, const vslam_match_params *params, int32_t *d_kp_of_point,
-                       int32_t *d_dist, double *d_corr_points, float *d_corr_xy, int32_t *d_corr_point, int32_t *d_corr_kp,
-                       int32_t *d_n_corr, int32_t *d_stats) {
-    if (!ctx) return VSLAM_ERR_INVALID;
-    VS_REQUIRE(ctx, d_points && d_n_points && d_obs_offsets && d_obs_desc && d_xy && d_desc && d_n_kp, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, d_kp_of_point && d_dist && d_corr_points && d_corr_xy && d_n_corr, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, batch > 0 && pt_stride > 0 && obs_stride > 0 && kp_stride > 0, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, kp_stride <= VSLAM_MAX_KP, VSLAM_ERR_CAPACITY);
-    vslam_match_params p;
-    vslam_match_params_default(&p);
-    if (params) p = *params;
-    VS_REQUIRE(ctx, match_params_ok(p), VSLAM_ERR_INVALID);
-    VS_ALIGNED(ctx, d_points, 16);   // float4 rows
-    VS_ALIGNED(ctx, d_desc, 16);     // descriptor rows move as uint4 pairs
-    VS_ALIGNED(ctx, d_obs_desc, 16);
-    VS_ALIGNED(ctx, d_xy, 8);        // float2 rows
-    VS_ALIGNED(ctx, d_corr_xy, 8);
-    VS_ALIGNED(ctx, d_corr_points, 8);
-    VS_REQUIRE(ctx, vs_ptr_bits(d_n_points, d_obs_offsets, d_n_kp, d_kp_taken, d_kp_of_point, d_dist, d_corr_point, d_corr_kp, d_n_corr,
-                                d_stats) % 4 == 0, VSLAM_ERR_INVALID);
-    MatchArgs a;
-    a.points = reinterpret_cast<const float4 *>(d_points); a.n_points = d_n_points; a.pt_stride = pt_stride;
-    a.obs_offsets = d_obs_offsets; a.obs_desc = d_obs_desc; a.obs_stride = obs_stride;
-    a.xy = reinterpret_cast<const float2 *>(d_xy); a.desc = d_desc; a.n_kp = d_n_kp; a.kp_stride = kp_stride; a.taken = d_kp_taken;
-    a.prm = vs_search::ss_params(1.0, p.dist_threshold, p.ratio10);   // no disc: the radius is not read
-    a.keys = nullptr; a.prop = nullptr;
-    a.kp_of_point = d_kp_of_point; a.dist = d_dist; a.corr_points = d_corr_points; a.corr_xy = reinterpret_cast<float2 *>(d_corr_xy);
-    a.corr_point = d_corr_point; a.corr_kp = d_corr_kp; a.n_corr = d_n_corr; a.stats = d_stats;
-    return launch_match(ctx, a, batch);
-}
-
 int vslam_world_relocalise(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const float *d_xy_cur, const uint8_t *d_desc_cur,
                            const int32_t *d_n_cur, const float *h_K, const uint32_t *d_seeds, const vslam_match_params *match,
                            const vslam_pnp_params *pnp, const vslam_resect_params *polish, int32_t *d_found, int32_t *d_winner,
@@ -553,14 +302,6 @@ int vslam_world_relocalise(vslam_ctx *ctx, vslam_world *world, vslam_map *map, c
     if (!ctx) return VSLAM_ERR_INVALID;
     VS_REQUIRE(ctx, world && map && d_xy_cur && d_desc_cur && d_n_cur && h_K && d_seeds, VSLAM_ERR_INVALID);
     VS_REQUIRE(ctx, d_found && d_winner && d_n_inliers && d_corr_point && d_corr_kp && d_n_corr, VSLAM_ERR_INVALID);
-    VS_REQUIRE(ctx, world->ctx == ctx && vs_map_world(map) == world && world->world_points, VSLAM_ERR_INVALID);
-    vslam_map_arrays m;
-    int rc = vslam_map_view(map, &m);
-    if (rc != VSLAM_OK) return rc;
-    VS_REQUIRE(ctx, m.frames == world->frames && m.frames >= 1, VSLAM_ERR_INVALID);
-    VS_ALIGNED(ctx, d_xy_cur, 8);
-    VS_ALIGNED(ctx, d_desc_cur, 16);
-    VS_ALIGNED(ctx, d_stats, 8);
     VS_REQUIRE(ctx, vs_ptr_bits(d_n_cur, d_seeds, d_found, d_winner, d_n_inliers, d_corr_point, d_corr_kp, d_n_corr) % 4 == 0, VSLAM_ERR_INVALID);
     vslam_match_params mp;
     vslam_match_params_default(&mp);
@@ -568,31 +309,28 @@ int vslam_world_relocalise(vslam_ctx *ctx, vslam_world *world, vslam_map *map, c
     vslam_pnp_params pp;
     vslam_pnp_params_default(&pp);
     if (pnp) pp = *pnp;
-    VS_REQUIRE(ctx, match_params_ok(mp) && params_ok(pp) && (!polish || vs_resect_params_ok(*polish)), VSLAM_ERR_INVALID);
-    const int T = m.tracks, P = m.map_capacity, O = m.obs_capacity, Kp = m.kp_stride;
-    // workspace: the map's CSR and its descriptors, the per-point outputs of the match, what was matched, the mask and the inliers
+    VS_REQUIRE(ctx, vs_match_params_ok(mp) && params_ok(pp) && (!polish || vs_resect_params_ok(*polish)), VSLAM_ERR_INVALID);
+    VsWorldCorr c;   // R, T: the winner's pose; mark: a number in [3] where the track was found
+    int rc;
+    if ((rc = vs_world_corr_begin(ctx, world, map, d_xy_cur, d_desc_cur, d_stats, &c))) return rc;
+    const int T = c.m.tracks, Kp = c.m.kp_stride;
+    // beside the shared workspace: the winner's inliers (points, xy) and its mask
     void *ptr = nullptr;
-    if ((rc = vs_arena_get(ctx, "relocalise_i32", sizeof(int32_t) * (size_t)T * ((size_t)(P + 1) + 2 * (size_t)P + (size_t)Kp), &ptr))) return rc;
-    int32_t *off = static_cast<int32_t *>(ptr), *kp_of_point = off + (size_t)T * (P + 1), *dist = kp_of_point + (size_t)T * P,
-            *inlier = dist + (size_t)T * P;
-    if ((rc = vs_arena_get(ctx, "relocalise_desc", (size_t)T * O * VSLAM_DESC_BYTES, &ptr))) return rc;
-    uint8_t *obs_desc = static_cast<uint8_t *>(ptr);
-    if ((rc = vs_arena_get(ctx, "relocalise_f64", sizeof(double) * (size_t)T * (16 + 6 * (size_t)Kp), &ptr))) return rc;
-    double *R = static_cast<double *>(ptr), *Tr = R + (size_t)T * 9, *mark = Tr + (size_t)T * 3, *corr_points = mark + (size_t)T * 4,
-           *in_points = corr_points + (size_t)T * Kp * 3;
-    if ((rc = vs_arena_get(ctx, "relocalise_xy", sizeof(float) * 4 * (size_t)T * Kp, &ptr))) return rc;
-    float *corr_xy = static_cast<float *>(ptr), *in_xy = corr_xy + (size_t)T * Kp * 2;
-    if ((rc = vslam_map_observation_descriptors(ctx, map, off, obs_desc))) return rc;
-    if ((rc = vslam_match_points(ctx, world->world_points, static_cast<const int32_t *>(m.d_sizes), P, off, obs_desc, O, d_xy_cur, d_desc_cur,
-                                 d_n_cur, Kp, nullptr, T, &mp, kp_of_point, dist, corr_points, corr_xy, d_corr_point, d_corr_kp, d_n_corr,
-                                 nullptr)))
+    const size_t rows = (size_t)T * Kp;
+    if ((rc = vs_arena_get(ctx, "relocalise_inliers", rows * (3 * sizeof(double) + 2 * sizeof(float) + sizeof(int32_t)), &ptr))) return rc;
+    double *in_points = static_cast<double *>(ptr);
+    float *in_xy = reinterpret_cast<float *>(in_points + (size_t)T * Kp * 3);
+    int32_t *inlier = reinterpret_cast<int32_t *>(in_xy + (size_t)T * Kp * 2);
+    if ((rc = vslam_match_points(ctx, world->world_points, static_cast<const int32_t *>(c.m.d_sizes), c.m.map_capacity, c.off, c.obs_desc,
+                                 c.m.obs_capacity, d_xy_cur, d_desc_cur, d_n_cur, Kp, nullptr, T, &mp, c.kp_of_point, c.dist, c.corr_points,
+                                 c.corr_xy, d_corr_point, d_corr_kp, d_n_corr, nullptr)))
         return rc;
-    if ((rc = vslam_pnp_ransac(ctx, corr_points, corr_xy, d_n_corr, T, Kp, h_K, d_seeds, &pp, polish, R, Tr, inlier, in_points, in_xy, nullptr,
-                               d_n_inliers, d_winner, nullptr, d_stats)))
+    if ((rc = vslam_pnp_ransac(ctx, c.corr_points, c.corr_xy, d_n_corr, T, Kp, h_K, d_seeds, &pp, polish, c.R, c.T, inlier, in_points, in_xy,
+                               nullptr, d_n_inliers, d_winner, nullptr, d_stats)))
         return rc;
-    relocalise_mark_kernel<<<vs_div_up(T, kPT), kPT, 0, ctx->stream>>>(d_winner, T, mark, d_found);
+    relocalise_mark_kernel<<<vs_div_up(T, kPT), kPT, 0, ctx->stream>>>(d_winner, T, c.mark, d_found);
     VS_HIP(ctx, hipGetLastError());
-    return vs_world_search_writeback(ctx, world, m.frames - 1, R, Tr, mark);
+    return vs_world_search_writeback(ctx, world, c.m.frames - 1, c.R, c.T, c.mark);
 }
 
 }  // extern "C"
