@@ -4,13 +4,17 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect] [--adjust] [--search] [--relocalise]] [output directory]
+    python examples/render_map.py [--world [--resect] [--fuse [--cull]] [--adjust] [--search] [--relocalise]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
 and on the right the same points and frusta in one coordinate system (vslam_world_render), seen from the same viewpoint.
 --resect (with --world): every frame's pose is resected against the world's points (include/vslam_resect.h) instead of being
 chained from the pair's fundamental matrix alone; the accepted steps and participants per pair are printed.
+--fuse (with --world): after the last step, before anything else, the map points that share an observation are fused into tracks
+(World.fuse, include/vslam_fuse.h) and, with --cull, the points their observations do not support are culled (World.cull, at its
+untuned defaults); the world is drawn before and after (track*_before_fuse.ppm / track*_after_fuse.ppm) and the counts are printed.
+--adjust, --search and --relocalise then read the merged observation lists.
 --adjust (with --world): after the last step the last window of 8 frames and the points they observe are adjusted together
 (World.adjust, include/vslam_adjust.h) and the world is drawn once more: track*_before_adjust.ppm / track*_after_adjust.ppm.
 --search (with --world): after the last step (and after --adjust) the last frame is searched by projection against the WHOLE map
@@ -41,14 +45,18 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--adjust", "--search", "--relocalise")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--fuse", "--cull", "--adjust", "--search", "--relocalise")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
     adjust = "--adjust" in sys.argv[1:]
     search = "--search" in sys.argv[1:]
     relocalise = "--relocalise" in sys.argv[1:]
-    if (resect or adjust or search or relocalise) and not with_world:
-        sys.exit("--resect, --adjust, --search and --relocalise need --world")
+    fuse = "--fuse" in sys.argv[1:]
+    cull = "--cull" in sys.argv[1:]
+    if (resect or adjust or search or relocalise or fuse) and not with_world:
+        sys.exit("--resect, --fuse, --adjust, --search and --relocalise need --world")
+    if cull and not fuse:
+        sys.exit("--cull needs --fuse")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -103,6 +111,21 @@ def main():
             st = v["resect_stats"][0, 1:]
             print("resection, track 0: participants", [int(x) for x in st[:, 0]], "accepted steps",
                   [None if np.isnan(x) else int(x) for x in st[:, 3]])
+        if fuse:
+            world.render(pmap, view, W, H, out=(world_images, None))
+            before = world_images.cpu().numpy()
+            fs = world.fuse(pmap).cpu().numpy()
+            cs = world.cull(pmap, out["xy"], K).cpu().numpy() if cull else None
+            world.render(pmap, view, W, H, out=(world_images, None))
+            ctx.synchronize()
+            after = world_images.cpu().numpy()
+            for t in range(tracks):
+                write_ppm(os.path.join(out_dir, f"track{t}_before_fuse.ppm"), before[t])
+                write_ppm(os.path.join(out_dir, f"track{t}_after_fuse.ppm"), after[t])
+            print("fused per track: points", fs[:, 0].tolist(), "groups with more than one member", fs[:, 1].tolist(), "absorbed", fs[:, 2].tolist(),
+                  "observations kept", fs[:, 3].tolist())
+            if cull:
+                print("culled per track: taking part", cs[:, 0].tolist(), "kept", cs[:, 1].tolist(), "culled", cs[:, 2].tolist())
         if adjust:
             world.render(pmap, view, W, H, out=(world_images, None))
             before = world_images.cpu().numpy()

@@ -12,6 +12,7 @@
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
+#include "../vslam_fuse.h"
 
 namespace vslam {
 
@@ -101,6 +102,28 @@ public:
         check(vslam_world_relocalise(ctx_, world_, map, d_xy_cur, d_desc_cur, d_n_cur, h_K, d_seeds, match, pnp, polish, d_found, d_winner,
                                      d_n_inliers, d_corr_point, d_corr_kp, d_n_corr, d_stats),
               "vslam_world_relocalise");
+    }
+    // The map points of every track that share an observation fused into groups (vslam_world_fuse, include/vslam_fuse.h): the
+    // world's d_fuse_to written, the rows of the newly absorbed points in d_world_points set to NaN.  The world must be the one
+    // attached to `map`; d_stats [tracks][4] int32 or nullptr.
+    void fuse(vslam_map *map, int32_t *d_stats = nullptr) { check(vslam_world_fuse(ctx_, world_, map, d_stats), "vslam_world_fuse"); }
+    // The world points their observations do not support culled (vslam_world_cull, include/vslam_fuse.h); d_xy as adjust() takes it;
+    // params: nullptr for the defaults; d_stats [tracks][4] int32 or nullptr.
+    void cull(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, const vslam_cull_params *params = nullptr,
+              int32_t *d_stats = nullptr) {
+        check(vslam_world_cull(ctx_, world_, map, d_xy, xy_frames, h_K, params, d_stats), "vslam_world_cull");
+    }
+    // The CSR of the map's observations as this world sees it -- merged once a fusion exists, the map's own otherwise
+    // (vslam_world_observations, include/vslam_fuse.h): d_offsets [tracks][map_capacity + 1], d_frame_ids / d_point_ids
+    // [tracks][obs_capacity], d_desc [tracks][obs_capacity][32] or nullptr.
+    void observations(vslam_map *map, int32_t *d_offsets, int32_t *d_frame_ids, int32_t *d_point_ids, uint8_t *d_desc = nullptr) {
+        check(vslam_world_observations(ctx_, world_, map, d_offsets, d_frame_ids, d_point_ids, d_desc), "vslam_world_observations");
+    }
+    // [tracks][map_capacity] int32 on the device, nullptr while there is no fusion; *state: bit 0 fused, bit 1 culled
+    int32_t *fuse_to(int32_t *state = nullptr) const {
+        int32_t *d = nullptr;
+        check(vslam_world_fusion_view(world_, &d, state), "vslam_world_fusion_view");
+        return d;
     }
     vslam_world *handle() const { return world_; }
 

@@ -10,6 +10,7 @@
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
+#include "../vslam_fuse.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -99,6 +100,21 @@ void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s3
                 const unsigned int *d_seeds, f64 *d_R, f64 *d_T, s32 *d_inlier, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_index,
                 s32 *d_n_inliers, s32 *d_winner, s32 *d_counts = nullptr, f64 *d_stats = nullptr, const vslam_pnp_params *params = nullptr,
                 const vslam_resect_params *polish = nullptr);
+
+// Map points that share an observation grouped, their observation lists merged, for a batch of items the caller holds on the
+// device (vslam_fuse_points, include/vslam_fuse.h: the arrays and strides are that call's).  d_mask, d_out_src and d_stats may be
+// nullptr.  Stream-ordered on `ctx`; throws std::runtime_error with vslam_last_error.
+void fuse_points(vslam_ctx *ctx, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const s32 *d_obs_kp,
+                 int obs_stride, int cam_stride, int kp_stride, const s32 *d_mask, int batch, s32 *d_fuse_to, s32 *d_out_offsets,
+                 s32 *d_out_cam, s32 *d_out_kp, s32 *d_out_src = nullptr, s32 *d_stats = nullptr);
+
+// Which points of each item their observations support (vslam_cull_points, include/vslam_fuse.h: the arrays and strides are that
+// call's).  K: 3 x 3 CV_32F; params: nullptr for the defaults; d_counts may be nullptr.  Stream-ordered on `ctx`; throws
+// std::runtime_error with vslam_last_error.
+void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam,
+                 const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride, const float *d_xy,
+                 int kp_stride, const cv::Mat &K, int batch, s32 *d_keep, s32 *d_stats, s32 *d_counts = nullptr,
+                 const vslam_cull_params *params = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

@@ -106,6 +106,17 @@ class MatchParams(_Params):
     _fields_ = [("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
 
 
+# every symbol include/vslam_fuse.h declares (a header of its own; tests/test_gpu_fuse.py checks it)
+FUSE_SYMBOLS = ["vslam_cull_params_default", "vslam_fuse_points", "vslam_cull_points", "vslam_world_fuse", "vslam_world_cull",
+                "vslam_world_observations", "vslam_world_fusion_view"]
+
+
+class CullParams(_Params):
+    _struct = "vslam_cull_params"
+    _fields_ = [("inlier_px", C.c_double), ("min_good", C.c_int32), ("mature_good", C.c_int32), ("mature_age", C.c_int32),
+                ("good10", C.c_int32)]
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -593,6 +604,54 @@ class Context:
         out and the returned dict as search_projection's."""
         return self._correspond(self.lib.vslam_match_points, MatchParams, params, (), (), points, n_points, obs_offsets, obs_desc, xy, desc,
                                 n_kp, kp_taken, out, want_indices, want_stats)
+
+    def fuse_points(self, n_points, obs_offsets, obs_cam, obs_kp, cam_stride, kp_stride, mask=None, out=None, want_src=True, want_stats=True):
+        """vslam_fuse_points (include/vslam_fuse.h): each item's n_points (B,) i32 points with their observations in CSR (obs_offsets
+        (B, S + 1), obs_cam / obs_kp (B, O) i32) grouped by shared (cam, kp); mask (B, S) i32 or None: a point with a value < 0 takes no
+        part.  out: a dict of output tensors to write into (missing ones are made, zero-filled).  Returns the dict: fuse_to (B, S);
+        out_offsets (B, S + 1); out_cam, out_kp (B, O); out_src (B, O) (want_src); stats (B, 4) (want_stats), all i32."""
+        torch = self.torch
+        B, S, O = obs_offsets.shape[0], obs_offsets.shape[1] - 1, obs_cam.shape[1]
+        for x, nm in ((n_points, "n_points"), (obs_offsets, "obs_offsets"), (obs_cam, "obs_cam"), (obs_kp, "obs_kp"), (mask, "mask")):
+            self._dev(x, torch.int32, nm)
+        shapes = dict(fuse_to=((B, S), torch.int32), out_offsets=((B, S + 1), torch.int32), out_cam=((B, O), torch.int32),
+                      out_kp=((B, O), torch.int32))
+        if want_src:
+            shapes.update(out_src=((B, O), torch.int32))
+        if want_stats:
+            shapes.update(stats=((B, 4), torch.int32))
+        o = self._outputs(out, shapes, obs_offsets.device)
+        self._ready()
+        self._check(self.lib.vslam_fuse_points(
+            self.handle, _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), C.c_int(O), C.c_int(cam_stride),
+            C.c_int(kp_stride), _ptr(mask), C.c_int(B), _ptr(o["fuse_to"]), _ptr(o["out_offsets"]), _ptr(o["out_cam"]), _ptr(o["out_kp"]),
+            _ptr(o.get("out_src")), _ptr(o.get("stats"))))
+        return o
+
+    def cull_points(self, points, n_points, obs_offsets, obs_cam, obs_kp, R, T, n_cams, xy, K, out=None, want_counts=True, **params):
+        """vslam_cull_points (include/vslam_fuse.h): which of each item's points (B, S, 4) f32 their observations (CSR as
+        fuse_points takes it) support under the cameras R (B, Cs, 9) / T (B, Cs, 3) f64, n_cams (B,) i32 of them, with keypoints xy
+        (B, Cs, Kp, 2) f32 and K (the 3 x 3 camera matrix, host); params: fields of vslam_cull_params over its defaults.  Returns a
+        dict: keep (B, S); counts (B, S, 2) (want_counts); stats (B, 4), all i32."""
+        import numpy as np
+        torch = self.torch
+        B, S, O, Cs, Kp = points.shape[0], points.shape[1], obs_cam.shape[1], R.shape[1], xy.shape[2]
+        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
+                          (obs_cam, torch.int32, "obs_cam"), (obs_kp, torch.int32, "obs_kp"), (R, torch.float64, "R"), (T, torch.float64, "T"),
+                          (n_cams, torch.int32, "n_cams"), (xy, torch.float32, "xy")):
+            self._dev(x, dt, nm)
+        shapes = dict(keep=((B, S), torch.int32), stats=((B, 4), torch.int32))
+        if want_counts:
+            shapes.update(counts=((B, S, 2), torch.int32))
+        o = self._outputs(out, shapes, points.device)
+        prm = CullParams.make(self.lib, **params)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        self._ready()
+        self._check(self.lib.vslam_cull_points(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), C.c_int(O), _ptr(R), _ptr(T),
+            _ptr(n_cams), C.c_int(Cs), _ptr(xy), C.c_int(Kp), Kh.ctypes.data_as(C.c_void_p), C.c_int(B), C.byref(prm), _ptr(o["keep"]),
+            _ptr(o.get("counts")), _ptr(o["stats"])))
+        return o
 
     def kdtree_build(self, xy, n):
         torch = self.torch
@@ -1123,6 +1182,46 @@ class World:
                                                     Kh.ctypes.data_as(C.c_void_p), C.c_int(window), C.byref(prm), _ptr(stats)))
         return stats
 
+    def fuse(self, pmap):
+        """vslam_world_fuse (include/vslam_fuse.h): the map points of every track that share an observation fused into groups; this
+        world must be the one attached to `pmap`.  Returns the statistics (tracks, 4) i32 (a cuda tensor): points taking part, groups
+        with more than one member, points absorbed, entries kept."""
+        torch = self.ctx.torch
+        stats = torch.zeros((self.tracks, 4), dtype=torch.int32, device=self.ctx.device)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_fuse(self.ctx.handle, self.handle, pmap.handle, _ptr(stats)))
+        return stats
+
+    def cull(self, pmap, xy, K, **params):
+        """vslam_world_cull (include/vslam_fuse.h): the world points their observations do not support culled; xy: the keypoints of
+        every frame as adjust() takes them; params: fields of vslam_cull_params over its defaults.  Returns the statistics
+        (tracks, 4) i32 (a cuda tensor): points taking part, kept, culled, good observations."""
+        import numpy as np
+        torch = self.ctx.torch
+        self.ctx._dev(xy, torch.float32, "xy")
+        xy_frames = xy.numel() // (self.tracks * self.kp_stride * 2)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.zeros((self.tracks, 4), dtype=torch.int32, device=xy.device)
+        prm = CullParams.make(self.lib, **params)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_cull(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), C.c_int(xy_frames),
+                                                  Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
+        return stats
+
+    def observations(self, pmap, desc=True):
+        """vslam_world_observations (include/vslam_fuse.h): the CSR of the map's observations as this world sees it -- merged once a
+        fusion exists, the map's own otherwise --: (offsets [tracks][map_capacity + 1], frame_ids, point_ids [tracks][obs_capacity]
+        i32, desc [tracks][obs_capacity][32] u8 or None) as cuda tensors, stream-ordered; slots past a track's total hold -1 / 0."""
+        torch = self.ctx.torch
+        dev = self.ctx.device
+        off = torch.zeros((self.tracks, pmap.map_capacity + 1), dtype=torch.int32, device=dev)
+        fr = torch.full((self.tracks, pmap.obs_capacity), -1, dtype=torch.int32, device=dev)
+        pt = torch.full((self.tracks, pmap.obs_capacity), -1, dtype=torch.int32, device=dev)
+        d = torch.zeros((self.tracks, pmap.obs_capacity, 32), dtype=torch.uint8, device=dev) if desc else None
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_observations(self.ctx.handle, self.handle, pmap.handle, _ptr(off), _ptr(fr), _ptr(pt), _ptr(d)))
+        return off, fr, pt, d
+
     def search(self, pmap, cur, K, width, height, resect=None, **params):
         """vslam_world_search (include/vslam_search.h): every track's world points searched by projection, from the pose of the last
         frame recorded, in the frame `cur` (a dict of xy (tracks, kp_stride, 2) f32, desc (tracks, kp_stride, 32) u8, n (tracks,)
@@ -1238,6 +1337,10 @@ class World:
         self.ctx._check(self.lib.vslam_world_resection_view(self.handle, C.byref(stats)))
         if stats.value:   # PointMap.view() shows it as world_resect_stats
             v["resect_stats"] = get(stats.value, (T, Fr, 4), np.float64)
+        fuse_to = C.c_void_p()
+        self.ctx._check(self.lib.vslam_world_fusion_view(self.handle, C.byref(fuse_to), C.c_void_p(0)))
+        if fuse_to.value:   # only while a fusion exists; PointMap.view() shows it as world_fuse_to
+            v["fuse_to"] = get(fuse_to.value, (T, int(a.map_capacity)), np.int32)
         return v
 
     def render(self, pmap, view, width, height, tracks=None, depth=False, row_stride=None, out=None):

@@ -348,7 +348,7 @@ int vslam_world_adjust(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const
     g.sizes = static_cast<const int32_t *>(m.d_sizes);
     g.Twc = world->Twc; g.pose = world->pose; g.world_points = world->world_points; g.carry = world->carry; g.carry_idx = world->carry_idx;
     g.d_xy = d_xy;
-    if ((rc = vslam_map_observations(ctx, map, g.log_off, g.log_frame, g.log_kp))) return rc;
+    if ((rc = vs_world_csr(ctx, world, map, g.log_off, g.log_frame, g.log_kp, nullptr))) return rc;
     world_adjust_gather_kernel<<<T, kAT, 0, ctx->stream>>>(g);
     VS_HIP(ctx, hipGetLastError());
     AdArgs a;

@@ -365,6 +365,10 @@ struct vslam_world {
     double *carry_next = nullptr;        // [tracks][kp_stride][3]
     int32_t *carry_idx_next = nullptr;   // [tracks][kp_stride]
     double *resect_stats = nullptr;      // [tracks][max_frames][4]
+    // include/vslam_fuse.h: made by the first vslam_world_fuse / vslam_world_cull.  fusion: bit 0 a fusion exists, bit 1 a cull has run;
+    // 0 = "no fusion", d_fuse_to (if made) the identity
+    int32_t *fuse_to = nullptr;          // [tracks][map_capacity]
+    int fusion = 0;
     std::vector<void *> owned;
 };
 int vs_world_bind(vslam_ctx *ctx, vslam_world *w, int map_capacity);
@@ -403,5 +407,12 @@ int vs_world_corr_begin(vslam_ctx *ctx, vslam_world *world, vslam_map *map, cons
 // vslam_world_search's write-back (search.hip): frame f1 of every track whose mark[4 b + 3] is a number gets (R, T) [tracks][9] /
 // [tracks][3] written as d_Twc / d_pose and the latest carry re-expressed
 int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double *R, double *T, double *mark);
+// fuse.hip.  The CSR of the map's observations as the world sees it, which every world call that reads observations obtains here:
+// off [tracks][map_capacity + 1]; frame and kp [tracks][obs_capacity] (both or neither); desc [tracks][obs_capacity][32] or null.
+// Without a fusion exactly the launches of vslam_map_observations (frame, kp given) and vslam_map_observation_descriptors (desc
+// given); with one, the map's lists fused with d_mask = d_fuse_to (include/vslam_fuse.h) and the descriptors gathered through
+// d_out_src.
+int vs_world_csr(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int32_t *off, int32_t *frame, int32_t *kp, uint8_t *desc);
+int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world);   // "no fusion": d_fuse_to (if made) the identity
 struct vslam_match_params;   // include/vslam_pnp.h
 bool vs_match_params_ok(const vslam_match_params &p);   // search.hip

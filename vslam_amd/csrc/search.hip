@@ -451,7 +451,7 @@ int vs_world_corr_begin(vslam_ctx *ctx, vslam_world *world, vslam_map *map, cons
     c->R = static_cast<double *>(ptr); c->T = c->R + T * 9; c->mark = c->T + T * 3; c->corr_points = c->mark + T * 4;
     if ((rc = vs_arena_get(ctx, "world_corr_xy", sizeof(float) * 2 * T * Kp, &ptr))) return rc;
     c->corr_xy = static_cast<float *>(ptr);
-    return vslam_map_observation_descriptors(ctx, map, c->off, c->obs_desc);
+    return vs_world_csr(ctx, world, map, c->off, nullptr, nullptr, c->obs_desc);
 }
 
 int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double *R, double *T, double *mark) {

@@ -307,6 +307,7 @@ int vslam_world_reset(vslam_ctx *ctx, vslam_world *world) {
     world_reset_kernel<<<world->tracks, kWT, 0, ctx->stream>>>(dev_of(world));
     VS_HIP(ctx, hipGetLastError());
     world->frames = 1;
+    if (int rc = vs_world_fusion_reset(ctx, world)) return rc;
     if (world->resect_stats) return vs_world_resect_reset(ctx, world);
     return VSLAM_OK;
 }

@@ -900,6 +900,25 @@ void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s3
                                     d_corr_xy, d_corr_index, d_n_inliers, d_winner, d_counts, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_pnp_ransac: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void fuse_points(vslam_ctx *ctx, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const s32 *d_obs_kp,
+                 int obs_stride, int cam_stride, int kp_stride, const s32 *d_mask, int batch, s32 *d_fuse_to, s32 *d_out_offsets,
+                 s32 *d_out_cam, s32 *d_out_kp, s32 *d_out_src, s32 *d_stats) {
+    const int rc = vslam_fuse_points(ctx, d_n_points, pt_stride, d_obs_offsets, d_obs_cam, d_obs_kp, obs_stride, cam_stride, kp_stride, d_mask,
+                                     batch, d_fuse_to, d_out_offsets, d_out_cam, d_out_kp, d_out_src, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_fuse_points: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
+void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam,
+                 const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride, const float *d_xy,
+                 int kp_stride, const cv::Mat &K, int batch, s32 *d_keep, s32 *d_stats, s32 *d_counts, const vslam_cull_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("cull_points: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_cull_points(ctx, d_points, d_n_points, pt_stride, d_obs_offsets, d_obs_cam, d_obs_kp, obs_stride, d_R, d_T, d_n_cams,
+                                     cam_stride, d_xy, kp_stride, k, batch, params, d_keep, d_counts, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_cull_points: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
