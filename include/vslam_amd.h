@@ -113,6 +113,18 @@ int vslam_corner_stats(vslam_ctx *ctx, uint64_t h_stats[5]);
 /* Device memory the context's grow-only workspaces hold at the moment (bytes; what a batch shape costs beside its own
  * inputs and outputs).                                                                                    */
 int vslam_ctx_workspace_bytes(vslam_ctx *ctx, size_t *bytes_out);
+/* Diagnostics of those workspaces.  The rule every entry point is held to (tests/test_gpu_workspace.py): what a
+ * call writes is a function of its arguments and of the resident state it is handed (maps, worlds), never of what an earlier
+ * call left in a workspace.  The named slots whose name begins with "ctx." are the only ones that carry anything from one call
+ * to the next (the default rBRIEF table, the sticky error word, a calibration target).
+ *   vslam_ctx_workspace_fill   queues one memset of `byte` (0 .. 255) per slot on the context's stream, stream-ordered like any
+ *       other call, no synchronisation; the "ctx." slots are left alone.  The next call of every entry point must give the bits it
+ *       gives on any other workspace contents.  vslam_corner_stats and the vslam_debug_* read-backs report a workspace's
+ *       contents and so report the fill when they are read behind it.
+ *   vslam_ctx_workspace_slots  the slots as text, one line "name bytes\n" per slot in name order, NUL-terminated, cut to `cap`
+ *       bytes when it is longer; *needed = the bytes the whole text takes, the NUL included.  buf may be NULL when cap is 0.  */
+int vslam_ctx_workspace_fill(vslam_ctx *ctx, int byte);
+int vslam_ctx_workspace_slots(vslam_ctx *ctx, char *buf, size_t cap, size_t *needed);
 const char *vslam_version(void);
 /* ORB's learned rBRIEF test pairs (OpenCV `bit_pattern_31_`, the table behind cv::ORB::compute, src/Frame.cpp:57,68):
  * HOST pointer to 256 x (x0, y0, x1, y1) int8, static storage.  Every d_pattern argument below accepts NULL for a

@@ -27,6 +27,8 @@ _BY_ENTRY = {
     "vslam_last_error": {"ctx": HOST},
     "vslam_corner_stats": {"ctx": HOST, "h_stats": HOST},
     "vslam_ctx_workspace_bytes": {"ctx": HOST, "bytes_out": HOST},
+    "vslam_ctx_workspace_fill": {"ctx": HOST},
+    "vslam_ctx_workspace_slots": {"ctx": HOST, "buf": HOST, "needed": HOST},
     "vslam_ctx_set_option": {"ctx": HOST},
     "vslam_dev_alloc": {"ctx": HOST, "d_out": HOST},
     "vslam_dev_free": {"ctx": HOST, "d_ptr": ANY},

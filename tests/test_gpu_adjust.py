@@ -359,20 +359,15 @@ def test_int32_arrays_at_four_bytes_and_f64_at_eight_give_the_aligned_bits(ctx, 
 
 
 def test_stream_order_behind_a_stalled_stream(cases):
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
         ctx = capi.Context(0)
         try:
             def make(name):
-                b = _batch([_item(cases[0][name][0])], 8, 300, 2400)
-                argv = [P("d_R"), P("d_T"), P("d_n_cams"), 8, P("d_points"), P("d_n_points"), 300, P("d_obs_offsets"), P("d_obs_cam"), P("d_obs_xy"),
-                        2400, 1, Hst("h_K"), C.c_void_p(0), P("d_stats")]
-                return Call("vslam_adjust_windows", argv,
-                            ins={"d_n_cams": b["nc"], "d_n_points": b["n"], "d_obs_offsets": b["off"], "d_obs_cam": b["cam"], "d_obs_xy": b["xy"]},
-                            inouts={"d_R": b["R"], "d_T": b["T"], "d_points": b["X"]}, outs={"d_stats": ((1, 4), torch.float64)},
-                            hosts={"h_K": KM.reshape(9).copy()})
+                return hc.adjust_windows(_batch([_item(cases[0][name][0])], 8, 300, 2400), KM)
             call, other = make("c8n257"), make("decided_c8n257")
             decoys = Decoys(call, other, None)
             sizing = choose_sizing(ctx, [call], stream)

@@ -414,7 +414,7 @@ def _behind_stall(make, entry, check):
 
 
 def test_fuse_stream_order_behind_a_stalled_stream():
-    from entry_calls import Call, P
+    import header_calls as hc
     items = [rf.random_fuse_item(61, 600, kp_stride=300), rf.random_fuse_item(62, 600, kp_stride=300)]
     O = max(len(it["cam"]) for it in items)
 
@@ -422,13 +422,7 @@ def test_fuse_stream_order_behind_a_stalled_stream():
         it = items[i]
         b = rf.batch_fuse([dict(it, cam=np.concatenate([it["cam"], np.zeros(O - len(it["cam"]), np.int32)]),
                                 kp=np.concatenate([it["kp"], np.zeros(O - len(it["kp"]), np.int32)]))])
-        S = b["offsets"].shape[1] - 1
-        argv = [P("d_n_points"), S, P("d_obs_offsets"), P("d_obs_cam"), P("d_obs_kp"), O, 6, 300, P("d_mask"), 1, P("d_fuse_to"), P("d_out_offsets"),
-                P("d_out_cam"), P("d_out_kp"), P("d_out_src"), P("d_stats")]
-        return Call("vslam_fuse_points", argv,
-                    ins={"d_n_points": _t(b["n"]), "d_obs_offsets": _t(b["offsets"]), "d_obs_cam": _t(b["cam"]), "d_obs_kp": _t(b["kp"]), "d_mask": _t(b["mask"])},
-                    outs={"d_fuse_to": ((1, S), torch.int32), "d_out_offsets": ((1, S + 1), torch.int32), "d_out_cam": ((1, O), torch.int32),
-                          "d_out_kp": ((1, O), torch.int32), "d_out_src": ((1, O), torch.int32), "d_stats": ((1, 4), torch.int32)})
+        return hc.fuse_points({k: _t(b[k]) for k in ("n", "offsets", "cam", "kp", "mask")}, 6, 300)
 
     def check(got):
         st = np.frombuffer(got["d_stats"].tobytes(), np.int32)
@@ -437,21 +431,12 @@ def test_fuse_stream_order_behind_a_stalled_stream():
 
 
 def test_cull_stream_order_behind_a_stalled_stream():
-    from entry_calls import Call, Hst, P
+    import header_calls as hc
     items = [rf.random_cull_item(71, 600, 6), rf.random_cull_item(72, 600, 6)]
     both = _cull_batch(items)                                          # one shape for the call and its decoys
 
     def make(i):
-        it = items[i]
-        b = {k: v[i:i + 1] for k, v in both.items()}
-        S, O, Cs, Kp = b["points"].shape[1], b["cam"].shape[1], b["R"].shape[1], b["xy"].shape[2]
-        argv = [P("d_points"), P("d_n_points"), S, P("d_obs_offsets"), P("d_obs_cam"), P("d_obs_kp"), O, P("d_R"), P("d_T"), P("d_n_cams"), Cs,
-                P("d_xy"), Kp, Hst("h_K"), 1, C.c_void_p(0), P("d_keep"), P("d_counts"), P("d_stats")]
-        return Call("vslam_cull_points", argv,
-                    ins={"d_points": _t(b["points"]), "d_n_points": _t(b["n"]), "d_obs_offsets": _t(b["offsets"]), "d_obs_cam": _t(b["cam"]),
-                         "d_obs_kp": _t(b["kp"]), "d_R": _t(b["R"]), "d_T": _t(b["T"]), "d_n_cams": _t(b["n_cams"]), "d_xy": _t(b["xy"])},
-                    outs={"d_keep": ((1, S), torch.int32), "d_counts": ((1, S, 2), torch.int32), "d_stats": ((1, 4), torch.int32)},
-                    hosts={"h_K": np.asarray(it["K"], np.float32).reshape(9).copy()})
+        return hc.cull_points({k: _t(v[i:i + 1]) for k, v in both.items()}, items[i]["K"])
 
     def check(got):
         st = np.frombuffer(got["d_stats"].tobytes(), np.int32)
@@ -831,7 +816,8 @@ def test_world_fuse_stream_order_behind_a_stalled_stream(ctx, scenes):
     """vslam_world_cull (its inputs are device arrays; vslam_world_fuse takes none) on the session's context, as
     test_gpu_pnp.test_world_relocalise_stream_order_behind_a_stalled_stream does it: the keypoints are the inputs, a noisy copy the
     decoys; the world is put back before every run and what the call leaves in it is compared beside its statistics."""
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.default_stream()
     assert torch.cuda.current_stream() == stream
@@ -859,9 +845,7 @@ def test_world_fuse_stream_order_behind_a_stalled_stream(ctx, scenes):
             if noise:
                 rng = np.random.default_rng(noise)
                 xy[:, 2:] += rng.uniform(-30, 30, xy[:, 2:].shape).astype(np.float32)
-            argv = [wa.handle, a.handle, P("d_xy"), 6, Hst("h_K"), C.c_void_p(0), P("d_stats")]
-            return Call("vslam_world_cull", argv, ins={"d_xy": _t(xy)}, outs={"d_stats": ((T, 4), torch.int32)}, before=before, state=state,
-                        hosts={"h_K": pc.SCENE_K.reshape(9).copy()})
+            return hc.world_cull(wa, a, _t(xy), 6, pc.SCENE_K, before, state)
         call, other = make(0), make(9)
         decoys = Decoys(call, other, None)
         sizing = choose_sizing(ctx, [call], stream)

@@ -244,7 +244,8 @@ def test_stream_order_behind_a_stalled_stream(ctx):
     """On the session's context and the stream it is bound to (torch's default stream): the test makes no stream and no context of
     its own, because every stream a process has made takes a place among the runtime's hardware queues and moves the streams
     that later tests make (tests/test_gpu_stream_order.py holds an upload path to a queue of its own)."""
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.default_stream()
     assert torch.cuda.current_stream() == stream
@@ -252,18 +253,8 @@ def test_stream_order_behind_a_stalled_stream(ctx):
 
     def make(seed):
         c = pc.case(rp.planted(300, 0.5, seed), seed=seed)
-        d = _tensors(c)
-        S, H = 300, c["params"]["hypotheses"]
-        argv = [P("d_points"), P("d_xy"), P("d_n"), 1, S, Hst("h_K"), P("d_seeds"), C.byref(structs[0]), C.byref(structs[1]), P("d_R"), P("d_T"),
-                P("d_inlier"), P("d_corr_points"), P("d_corr_xy"), P("d_corr_index"), P("d_n_inliers"), P("d_winner"), P("d_counts"),
-                P("d_stats")]
-        return Call("vslam_pnp_ransac", argv,
-                    ins={"d_points": d["points"], "d_xy": d["xy"], "d_n": d["n"], "d_seeds": d["seeds"]},
-                    inouts={"d_R": d["R"], "d_T": d["T"]},
-                    outs={"d_inlier": ((1, S), torch.int32), "d_corr_points": ((1, S, 3), torch.float64), "d_corr_xy": ((1, S, 2), torch.float32),
-                          "d_corr_index": ((1, S), torch.int32), "d_n_inliers": ((1,), torch.int32), "d_winner": ((1,), torch.int32),
-                          "d_counts": ((1, H, 4), torch.int32), "d_stats": ((1, 4), torch.float64)},
-                    hosts={"h_K": np.asarray(c["K"], np.float32).reshape(9).copy()})
+        assert c["params"]["hypotheses"] == structs[0].hypotheses
+        return hc.pnp_ransac(_tensors(c), c["K"], *structs)
     call, other = make(5), make(6)
     decoys = Decoys(call, other, None)
     sizing = choose_sizing(ctx, [call], stream)
@@ -304,6 +295,16 @@ def _match_batch(items):
         if c["taken"] is not None:
             taken[i, :len(c["taken"])] = c["taken"]
     return b, taken
+
+
+def _match_tensors(c, obs_stride):
+    """one item's arrays on the device, its observation rows cut or zero-padded to obs_stride (one stride for a call and its decoy)"""
+    b, _ = _match_batch([c])
+    d = {k: torch.from_numpy(np.ascontiguousarray(v[:, :obs_stride] if k == "obs_desc" else v)).cuda() for k, v in b.items()}
+    short = obs_stride - d["obs_desc"].shape[1]
+    if short > 0:
+        d["obs_desc"] = torch.cat([d["obs_desc"], torch.zeros((1, short, 32), dtype=torch.uint8).cuda()], 1).contiguous()
+    return d
 
 
 def _match(ctx, items, **params):
@@ -464,25 +465,14 @@ def test_match_points_refusals(ctx):
 
 def test_match_points_stream_order_behind_a_stalled_stream(ctx):
     """as test_stream_order_behind_a_stalled_stream: on the session's context and the default stream, no stream of its own"""
-    from entry_calls import Call, Decoys, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.default_stream()
     assert torch.cuda.current_stream() == stream
 
     def make(seed):
-        b, _ = _match_batch([pc.match_case(seed, 300, (1, 4), 257)])
-        d = {k: torch.from_numpy(v[:, :900] if k == "obs_desc" else v).cuda() for k, v in b.items()}
-        if d["obs_desc"].shape[1] < 900:     # one obs_stride for the call and its decoy
-            d["obs_desc"] = torch.cat([d["obs_desc"], torch.zeros((1, 900 - d["obs_desc"].shape[1], 32), dtype=torch.uint8).cuda()], 1).contiguous()
-        argv = [P("d_points"), P("d_n_points"), 300, P("d_obs_offsets"), P("d_obs_desc"), 900, P("d_xy"), P("d_desc"), P("d_n_kp"), 257, C.c_void_p(0), 1,
-                C.c_void_p(0), P("d_kp_of_point"), P("d_dist"), P("d_corr_points"), P("d_corr_xy"), P("d_corr_point"), P("d_corr_kp"), P("d_n_corr"),
-                P("d_stats")]
-        return Call("vslam_match_points", argv,
-                    ins={"d_points": d["points"], "d_n_points": d["n_points"], "d_obs_offsets": d["offsets"], "d_obs_desc": d["obs_desc"],
-                         "d_xy": d["xy"], "d_desc": d["desc"], "d_n_kp": d["n_kp"]},
-                    outs={"d_kp_of_point": ((1, 300), torch.int32), "d_dist": ((1, 300), torch.int32), "d_corr_points": ((1, 257, 3), torch.float64),
-                          "d_corr_xy": ((1, 257, 2), torch.float32), "d_corr_point": ((1, 257), torch.int32), "d_corr_kp": ((1, 257), torch.int32),
-                          "d_n_corr": ((1,), torch.int32), "d_stats": ((1, 4), torch.int32)})
+        return hc.match_points(_match_tensors(pc.match_case(seed, 300, (1, 4), 257), 900))
     call, other = make(2), make(6)
     decoys = Decoys(call, other, None)
     sizing = choose_sizing(ctx, [call], stream)
@@ -843,7 +833,8 @@ def test_world_relocalise_stream_order_behind_a_stalled_stream(ctx):
     """vslam_world_relocalise behind a stalled stream, on the exact scenes and the session's context (no stream of its own): the last
     frame's arrays and the seeds are the inputs, another frame's the decoys; the world is put back before every run, and what the
     call leaves in the world is compared beside its outputs."""
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.default_stream()
     assert torch.cuda.current_stream() == stream
@@ -867,13 +858,7 @@ def test_world_relocalise_stream_order_behind_a_stalled_stream(ctx):
             return {k: v[k] for k in ("world_Twc", "world_pose", "world_carry", "world_scale", "world_links", "world_points", "points", "sizes")}
 
         def make(f, seed0):
-            argv = [wa.handle, a.handle, P("d_xy_cur"), P("d_desc_cur"), P("d_n_cur"), Hst("h_K"), P("d_seeds"), C.c_void_p(0), C.c_void_p(0),
-                    C.byref(polish), P("d_found"), P("d_winner"), P("d_n_inliers"), P("d_corr_point"), P("d_corr_kp"), P("d_n_corr"), P("d_stats")]
-            return Call("vslam_world_relocalise", argv, ins=frame(f, seed0),
-                        outs={"d_found": ((T,), torch.int32), "d_winner": ((T,), torch.int32), "d_n_inliers": ((T,), torch.int32),
-                              "d_corr_point": ((T, SCENE_KP), torch.int32), "d_corr_kp": ((T, SCENE_KP), torch.int32), "d_n_corr": ((T,), torch.int32),
-                              "d_stats": ((T, 4), torch.float64)},
-                        before=lambda: _restore(ctx, wa, start), state=state, hosts={"h_K": pc.SCENE_K.reshape(9).copy()})
+            return hc.world_relocalise(wa, a, frame(f, seed0), pc.SCENE_K, polish, lambda: _restore(ctx, wa, start), state)
         call, other = make(5, 1), make(3, 50)
         decoys = Decoys(call, other, None)
         sizing = choose_sizing(ctx, [call], stream)

@@ -272,7 +272,8 @@ def test_every_pointer_exactly_at_its_alignment_gives_the_aligned_bits(ctx, plan
 
 
 def test_stream_order_behind_a_stalled_stream(planted):
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     scenes, b, ref = planted
     stream = torch.cuda.Stream()
@@ -280,18 +281,7 @@ def test_stream_order_behind_a_stalled_stream(planted):
         ctx = capi.Context(0)
         try:
             def make(i):
-                d = _cuda({k: v[i:i + 1] for k, v in b.items()})
-                S, Kp, O = d["points"].shape[1], d["xy"].shape[1], d["obs_desc"].shape[1]
-                argv = [P("d_points"), P("d_n_points"), S, P("d_obs_offsets"), P("d_obs_desc"), O, P("d_R"), P("d_T"), Hst("h_K"), 640, 480,
-                        P("d_xy"), P("d_desc"), P("d_n_kp"), Kp, C.c_void_p(0), 1, C.c_void_p(0), P("d_kp_of_point"), P("d_dist"),
-                        P("d_corr_points"), P("d_corr_xy"), P("d_corr_point"), P("d_corr_kp"), P("d_n_corr"), P("d_stats")]
-                return Call("vslam_search_projection", argv,
-                            ins={"d_points": d["points"], "d_n_points": d["n_points"], "d_obs_offsets": d["offsets"], "d_obs_desc": d["obs_desc"],
-                                 "d_R": d["R"], "d_T": d["T"], "d_xy": d["xy"], "d_desc": d["desc"], "d_n_kp": d["n_kp"]},
-                            outs={"d_kp_of_point": ((1, S), torch.int32), "d_dist": ((1, S), torch.int32), "d_corr_points": ((1, Kp, 3), torch.float64),
-                                  "d_corr_xy": ((1, Kp, 2), torch.float32), "d_corr_point": ((1, Kp), torch.int32), "d_corr_kp": ((1, Kp), torch.int32),
-                                  "d_n_corr": ((1,), torch.int32), "d_stats": ((1, 4), torch.int32)},
-                            hosts={"h_K": np.asarray(scenes[0]["K"], np.float32).reshape(9).copy()})
+                return hc.search_projection(_cuda({k: v[i:i + 1] for k, v in b.items()}), scenes[0]["K"], 640, 480)
             call, other = make(0), make(1)
             decoys = Decoys(call, other, None)
             sizing = choose_sizing(ctx, [call], stream)
@@ -526,7 +516,8 @@ def test_world_search_errors(ctx, sequences):
 def test_world_search_stream_order_behind_a_stalled_stream(sequences):
     """the search-only call (it changes nothing of the world, so the plain run and the stalled run start from the same state):
     the current frame's arrays are the inputs, another frame's the decoys"""
-    from entry_calls import Call, Decoys, Hst, P
+    import header_calls as hc
+    from entry_calls import Decoys
     from stream_order import choose_sizing, run_behind_stall
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
@@ -538,12 +529,7 @@ def test_world_search_stream_order_behind_a_stalled_stream(sequences):
             ctx.synchronize()
 
             def make(f):
-                cur, _ = _frame_batches(out, f)
-                argv = [wa.handle, a.handle, P("d_xy_cur"), P("d_desc_cur"), P("d_n_cur"), Hst("h_K"), MW, MH, C.c_void_p(0), C.c_void_p(0),
-                        P("d_corr_point"), P("d_corr_kp"), P("d_n_corr"), C.c_void_p(0)]
-                return Call("vslam_world_search", argv, ins={"d_xy_cur": cur["xy"], "d_desc_cur": cur["desc"], "d_n_cur": cur["n"]},
-                            outs={"d_corr_point": ((TRACKS, MKP), torch.int32), "d_corr_kp": ((TRACKS, MKP), torch.int32),
-                                  "d_n_corr": ((TRACKS,), torch.int32)}, hosts={"h_K": _Kmat().reshape(9).copy()})
+                return hc.world_search(wa, a, _frame_batches(out, f)[0], _Kmat(), MW, MH)
             call, other = make(MF - 1), make(1)
             decoys = Decoys(call, other, None)
             sizing = choose_sizing(ctx, [call], stream)

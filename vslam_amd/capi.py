@@ -21,7 +21,7 @@ ERRORS = {-1: "VSLAM_ERR_INVALID", -2: "VSLAM_ERR_HIP", -3: "VSLAM_ERR_NO_DEVICE
 # every symbol include/vslam_amd.h declares (tests/test_capi_symbols.py checks the header too)
 SYMBOLS = [
     "vslam_ctx_create", "vslam_ctx_make_current", "vslam_ctx_destroy", "vslam_ctx_set_stream", "vslam_ctx_set_option", "vslam_ctx_synchronize", "vslam_ctx_wait",
-    "vslam_last_error", "vslam_ctx_workspace_bytes", "vslam_version", "vslam_brief_pattern_31", "vslam_dev_alloc", "vslam_dev_free", "vslam_copy_h2d",
+    "vslam_last_error", "vslam_ctx_workspace_bytes", "vslam_ctx_workspace_fill", "vslam_ctx_workspace_slots", "vslam_version", "vslam_brief_pattern_31", "vslam_dev_alloc", "vslam_dev_free", "vslam_copy_h2d",
     "vslam_copy_d2h", "vslam_debug_stream_copy", "vslam_debug_valu_calib", "vslam_prof_enable", "vslam_prof_reset", "vslam_prof_count", "vslam_prof_get",
     "vslam_match_knn2_ratio", "vslam_ransac_sets", "vslam_ransac_fundamental", "vslam_ransac_solve",
     "vslam_ransac_evaluate", "vslam_refit_fundamental", "vslam_refine_pairs", "vslam_kdtree_build",
@@ -271,6 +271,20 @@ class Context:
         n = C.c_size_t()
         self._check(self.lib.vslam_ctx_workspace_bytes(self.handle, C.byref(n)))
         return n.value
+
+    def workspace_fill(self, byte=0):
+        """vslam_ctx_workspace_fill: every workspace slot but the "ctx." ones set to `byte`, stream-ordered (a diagnostic: the next
+        call of any entry point must give the bits it gives on any other workspace contents)."""
+        self._ready()
+        self._check(self.lib.vslam_ctx_workspace_fill(self.handle, C.c_int(int(byte))))
+
+    def workspace_slots(self):
+        """vslam_ctx_workspace_slots: {slot name: bytes} of the context's workspaces at the moment."""
+        need = C.c_size_t()
+        self._check(self.lib.vslam_ctx_workspace_slots(self.handle, C.c_char_p(None), C.c_size_t(0), C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._check(self.lib.vslam_ctx_workspace_slots(self.handle, buf, C.c_size_t(need.value), C.byref(need)))
+        return {name: int(size) for name, size in (line.rsplit(" ", 1) for line in buf.value.decode().splitlines())}
 
     OPT_RANSAC_ALL_SUMS = 1
     OPT_RANSAC_MIN_MATCHES = 2

@@ -391,6 +391,32 @@ int vslam_ctx_workspace_bytes(vslam_ctx *ctx, size_t *bytes_out) {
     return VSLAM_OK;
 }
 
+// slots whose name begins with "ctx." carry state from call to call by design (the default pattern, the error word)
+static bool vs_arena_is_state(const std::string &name) { return name.compare(0, 4, "ctx.") == 0; }
+
+int vslam_ctx_workspace_fill(vslam_ctx *ctx, int byte) {
+    if (!ctx) return VSLAM_ERR_INVALID;
+    VS_REQUIRE(ctx, byte >= 0 && byte <= 255, VSLAM_ERR_INVALID);
+    for (const auto &kv : ctx->arena) {
+        if (vs_arena_is_state(kv.first) || !kv.second.ptr || !kv.second.bytes) continue;
+        VS_HIP(ctx, hipMemsetAsync(kv.second.ptr, byte, kv.second.bytes, ctx->stream));
+    }
+    return VSLAM_OK;
+}
+
+int vslam_ctx_workspace_slots(vslam_ctx *ctx, char *buf, size_t cap, size_t *needed) {
+    if (!ctx || !needed || (cap && !buf)) return VSLAM_ERR_INVALID;
+    std::string text;
+    for (const auto &kv : ctx->arena) text += kv.first + " " + std::to_string(kv.second.bytes) + "\n";
+    *needed = text.size() + 1;
+    if (cap) {
+        const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+        memcpy(buf, text.data(), n);
+        buf[n] = 0;
+    }
+    return VSLAM_OK;
+}
+
 int vslam_ctx_set_option(vslam_ctx *ctx, int option, int value) {
     if (!ctx) return VSLAM_ERR_INVALID;
     if (option == VSLAM_OPT_RANSAC_ALL_SUMS) {

@@ -285,6 +285,10 @@ struct VsCornerPool {
     uint8_t *state = nullptr;      // [slots][w * h]
     size_t key_cap = 0;
     int slots = 0;
+    // the frames' gray rows, for the selection's test of a frame that overflowed its list: a constant image has no corner and
+    // needs no slot (select.hip)
+    const uint8_t *gray = nullptr;
+    int pitch = 0;
 };
 #ifdef __HIPCC__
 __device__ __forceinline__ int vs_pool_used(const VsCornerPool &p) {

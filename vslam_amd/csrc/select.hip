@@ -531,7 +531,26 @@ __global__ __launch_bounds__(kST) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
     };
     if (bounded && raw_counts[f] > key_cap) {
-        to_pool();
+        // A constant image lists every interior pixel (tier 1's bound keeps its absolute margin, and nothing ever raises the
+        // threshold), yet it has no corner: every derivative of the reference is exactly 0, so is every response and the
+        // maximum, and nothing is above max * quality.  Such a frame is done here and takes no slot of the pool.  Any other
+        // frame leaves the scan at its first differing dword.
+        bool differs = pool.gray == nullptr;
+        if (!differs) {
+            const uint8_t *g = pool.gray + (size_t)f * pool.pitch * h;
+            const uint32_t first = g[0] * 0x01010101u;
+            const int w4 = w >> 2;
+            for (int i = tid; i < w4 * h && !differs; i += kST) {
+                const int y = i / w4, c = i - y * w4;
+                differs = *reinterpret_cast<const uint32_t *>(g + (size_t)y * pool.pitch + 4 * c) != first;
+            }
+            for (int i = tid; i < (w & 3) * h && !differs; i += kST) {
+                const int y = i / (w & 3), c = i - y * (w & 3);
+                differs = g[(size_t)y * pool.pitch + 4 * w4 + c] != g[0];
+            }
+        }
+        if (__syncthreads_or(differs)) to_pool();
+        else if (tid == 0) out_n[f] = 0;
         return;
     }
     if (n > key_cap) {
@@ -843,7 +862,8 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
     // (VSLAM_OPT_CORNER_LIST_CAP: another bound; -1: the whole image, which nothing can overflow).  A frame that does
     // overflow it (response plateaus, noise: every interior pixel can be listed), or whose selection needs per-pixel maps
     // (its rank window outgrew LDS), is filed in a small pool of whole-image scratch and redone from scratch by the plain
-    // exact pipeline (pass 2 below): results never depend on the bound.  Should more frames of one call need the pool
+    // exact pipeline (pass 2 below): results never depend on the bound.  (A CONSTANT image also lists every pixel; the
+    // selection tells it by its gray bytes and gives it no corners without a slot.)  Should more frames of one call need the pool
     // than it has slots, those frames get no corners and vslam_ctx_synchronize reports VSLAM_ERR_CAPACITY.
     // Gray rows that are no multiple of 4 bytes (a caller's packed image of such a width that nobody padded: widths below 64)
     // run the plain pipeline on whole-image buffers for every frame.
@@ -890,6 +910,8 @@ int vs_launch_good_features(vslam_ctx *ctx, const uint8_t *gray, int frames, int
         if ((rc = vs_arena_get(ctx, "gf.pool.keys", sizeof(unsigned long long) * px * pool.slots, (void **)&pool.keys))) return rc;
         if ((rc = vs_arena_get(ctx, "gf.pool.eig", sizeof(float) * px * pool.slots, (void **)&pool.eig))) return rc;
         if ((rc = vs_arena_get(ctx, "gf.pool.state", px * pool.slots, (void **)&pool.state))) return rc;
+        pool.gray = gray;   // (complete when the selection runs: formed by the detector's first kernel when it comes from a 3-byte image)
+        pool.pitch = pitch;
     } else {
         if ((rc = vs_arena_get(ctx, "gf.eig", sizeof(float) * px * frames, (void **)&eig))) return rc;
         if ((rc = vs_arena_get(ctx, "gf.state", px * frames, (void **)&state))) return rc;
