@@ -4,7 +4,7 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect] [--fuse [--cull]] [--adjust] [--search] [--relocalise]] [output directory]
+    python examples/render_map.py [--world [--resect] [--fuse [--cull] [--retriangulate]] [--adjust] [--search] [--relocalise]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
@@ -15,6 +15,9 @@ chained from the pair's fundamental matrix alone; the accepted steps and partici
 (World.fuse, include/vslam_fuse.h) and, with --cull, the points their observations do not support are culled (World.cull, at its
 untuned defaults); the world is drawn before and after (track*_before_fuse.ppm / track*_after_fuse.ppm) and the counts are printed.
 --adjust, --search and --relocalise then read the merged observation lists.
+--retriangulate (with --fuse, behind it and --cull): every world point is triangulated anew from ALL the observations of its merged
+row (World.retriangulate, include/vslam_tracks.h, at its untuned defaults); the world is drawn before and after
+(track*_before_retriangulate.ppm / track*_after_retriangulate.ppm) and the counts per status are printed.
 --adjust (with --world): after the last step the last window of 8 frames and the points they observe are adjusted together
 (World.adjust, include/vslam_adjust.h) and the world is drawn once more: track*_before_adjust.ppm / track*_after_adjust.ppm.
 --search (with --world): after the last step (and after --adjust) the last frame is searched by projection against the WHOLE map
@@ -45,7 +48,7 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--fuse", "--cull", "--adjust", "--search", "--relocalise")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--fuse", "--cull", "--retriangulate", "--adjust", "--search", "--relocalise")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
     adjust = "--adjust" in sys.argv[1:]
@@ -53,10 +56,11 @@ def main():
     relocalise = "--relocalise" in sys.argv[1:]
     fuse = "--fuse" in sys.argv[1:]
     cull = "--cull" in sys.argv[1:]
+    retri = "--retriangulate" in sys.argv[1:]
     if (resect or adjust or search or relocalise or fuse) and not with_world:
         sys.exit("--resect, --fuse, --adjust, --search and --relocalise need --world")
-    if cull and not fuse:
-        sys.exit("--cull needs --fuse")
+    if (cull or retri) and not fuse:
+        sys.exit("--cull and --retriangulate need --fuse")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -126,6 +130,18 @@ def main():
                   "observations kept", fs[:, 3].tolist())
             if cull:
                 print("culled per track: taking part", cs[:, 0].tolist(), "kept", cs[:, 1].tolist(), "culled", cs[:, 2].tolist())
+        if retri:
+            world.render(pmap, view, W, H, out=(world_images, None))
+            before = world_images.cpu().numpy()
+            status, ts = world.retriangulate(pmap, out["xy"], K)
+            world.render(pmap, view, W, H, out=(world_images, None))
+            ctx.synchronize()
+            after, status, ts = world_images.cpu().numpy(), status.cpu().numpy(), ts.cpu().numpy()
+            for t in range(tracks):
+                write_ppm(os.path.join(out_dir, f"track{t}_before_retriangulate.ppm"), before[t])
+                write_ppm(os.path.join(out_dir, f"track{t}_after_retriangulate.ppm"), after[t])
+            print("retriangulated per track: taking part", ts[:, 0].tolist(), "moved (OK)", ts[:, 1].tolist(), "low parallax", ts[:, 2].tolist(),
+                  "other refusals", ts[:, 3].tolist(), "; statuses 1 .. 6, track 0:", np.bincount(status[0][status[0] > 0], minlength=7)[1:].tolist())
         if adjust:
             world.render(pmap, view, W, H, out=(world_images, None))
             before = world_images.cpu().numpy()

@@ -13,6 +13,7 @@
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
 #include "../vslam_fuse.h"
+#include "../vslam_tracks.h"
 
 namespace vslam {
 
@@ -112,6 +113,13 @@ public:
     void cull(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, const vslam_cull_params *params = nullptr,
               int32_t *d_stats = nullptr) {
         check(vslam_world_cull(ctx_, world_, map, d_xy, xy_frames, h_K, params, d_stats), "vslam_world_cull");
+    }
+    // Every world point triangulated anew from all the observations of its row of the world's CSR, in place; only the rows that come
+    // out with status 0 are written (vslam_world_retriangulate, include/vslam_tracks.h).  d_xy as adjust() takes it; params: nullptr
+    // for the defaults; d_status [tracks][map_capacity] int32 or nullptr; d_stats [tracks][4] int32 or nullptr.
+    void retriangulate(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, const vslam_track_params *params = nullptr,
+                       int32_t *d_status = nullptr, int32_t *d_stats = nullptr) {
+        check(vslam_world_retriangulate(ctx_, world_, map, d_xy, xy_frames, h_K, params, d_status, d_stats), "vslam_world_retriangulate");
     }
     // The CSR of the map's observations as this world sees it -- merged once a fusion exists, the map's own otherwise
     // (vslam_world_observations, include/vslam_fuse.h): d_offsets [tracks][map_capacity + 1], d_frame_ids / d_point_ids

@@ -11,6 +11,7 @@
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
 #include "../vslam_fuse.h"
+#include "../vslam_tracks.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -115,6 +116,14 @@ void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, i
                  const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride, const float *d_xy,
                  int kp_stride, const cv::Mat &K, int batch, s32 *d_keep, s32 *d_stats, s32 *d_counts = nullptr,
                  const vslam_cull_params *params = nullptr);
+
+// Each point of each item triangulated from all its observations (vslam_triangulate_tracks, include/vslam_tracks.h: the arrays and
+// strides are that call's; d_out_points may be d_points).  K: 3 x 3 CV_32F; params: nullptr for the defaults; d_counts and d_info may
+// be nullptr.  Stream-ordered on `ctx`; throws std::runtime_error with vslam_last_error.
+void triangulate_tracks(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets,
+                        const s32 *d_obs_cam, const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams,
+                        int cam_stride, const float *d_xy, int kp_stride, const cv::Mat &K, int batch, float *d_out_points, s32 *d_status,
+                        s32 *d_stats, s32 *d_counts = nullptr, f64 *d_info = nullptr, const vslam_track_params *params = nullptr);
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

@@ -104,8 +104,9 @@
  * Workspace from the arena: vslam_fuse_points' own plus tracks x (2 map_capacity + 1 + 5 obs_capacity) x 4 bytes, and tracks x
  * obs_capacity x 32 where descriptors are gathered.
  *
- * Left open: geometric fusing through a search by projection (points that never shared a keypoint); a position chosen among the
- * members (the survivor keeps its own); a parallax test; running behind every step; tuning on footage.                        */
+ * Left open: geometric fusing through a search by projection (points that never shared a keypoint); running behind every step;
+ * tuning on footage.  The survivor keeps its own position here: vslam_world_retriangulate (vslam_tracks.h) gives every track the
+ * position all its observations support, with a parallax test as one of its refusals.                                          */
 #ifndef VSLAM_FUSE_H
 #define VSLAM_FUSE_H
 

@@ -117,6 +117,16 @@ class CullParams(_Params):
                 ("good10", C.c_int32)]
 
 
+# every symbol include/vslam_tracks.h declares (a header of its own; tests/test_gpu_tracks.py checks it)
+TRACK_SYMBOLS = ["vslam_track_params_default", "vslam_triangulate_tracks", "vslam_world_retriangulate"]
+
+
+class TrackParams(_Params):
+    _struct = "vslam_track_params"
+    _fields_ = [("cos_parallax_max", C.c_double), ("huber_px", C.c_double), ("inlier_px", C.c_double), ("iterations", C.c_int32),
+                ("min_good", C.c_int32), ("good10", C.c_int32)]
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -665,6 +675,35 @@ class Context:
             self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), C.c_int(O), _ptr(R), _ptr(T),
             _ptr(n_cams), C.c_int(Cs), _ptr(xy), C.c_int(Kp), Kh.ctypes.data_as(C.c_void_p), C.c_int(B), C.byref(prm), _ptr(o["keep"]),
             _ptr(o.get("counts")), _ptr(o["stats"])))
+        return o
+
+    def triangulate_tracks(self, points, n_points, obs_offsets, obs_cam, obs_kp, R, T, n_cams, xy, K, out=None, want_counts=True,
+                           want_info=True, **params):
+        """vslam_triangulate_tracks (include/vslam_tracks.h): each of an item's points (B, S, 4) f32 triangulated from all its
+        observations (CSR and cameras as cull_points takes them); params: fields of vslam_track_params over its defaults.  out: a dict
+        of output tensors to write into (out_points may be `points` itself); missing ones are made, zero-filled.  Returns the dict:
+        out_points (B, S, 4) f32; status (B, S) i32; counts (B, S, 2) i32 (want_counts); info (B, S, 3) f64 (want_info); stats (B, 4)
+        i32."""
+        import numpy as np
+        torch = self.torch
+        B, S, O, Cs, Kp = points.shape[0], points.shape[1], obs_cam.shape[1], R.shape[1], xy.shape[2]
+        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
+                          (obs_cam, torch.int32, "obs_cam"), (obs_kp, torch.int32, "obs_kp"), (R, torch.float64, "R"), (T, torch.float64, "T"),
+                          (n_cams, torch.int32, "n_cams"), (xy, torch.float32, "xy")):
+            self._dev(x, dt, nm)
+        shapes = dict(out_points=((B, S, 4), torch.float32), status=((B, S), torch.int32), stats=((B, 4), torch.int32))
+        if want_counts:
+            shapes.update(counts=((B, S, 2), torch.int32))
+        if want_info:
+            shapes.update(info=((B, S, 3), torch.float64))
+        o = self._outputs(out, shapes, points.device)
+        prm = TrackParams.make(self.lib, **params)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        self._ready()
+        self._check(self.lib.vslam_triangulate_tracks(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), C.c_int(O), _ptr(R), _ptr(T),
+            _ptr(n_cams), C.c_int(Cs), _ptr(xy), C.c_int(Kp), Kh.ctypes.data_as(C.c_void_p), C.c_int(B), C.byref(prm), _ptr(o["out_points"]),
+            _ptr(o["status"]), _ptr(o.get("counts")), _ptr(o.get("info")), _ptr(o["stats"])))
         return o
 
     def kdtree_build(self, xy, n):
@@ -1221,6 +1260,24 @@ class World:
         self.ctx._check(self.lib.vslam_world_cull(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), C.c_int(xy_frames),
                                                   Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
         return stats
+
+    def retriangulate(self, pmap, xy, K, want_status=True, **params):
+        """vslam_world_retriangulate (include/vslam_tracks.h): every world point triangulated anew from all the observations of its
+        row of the world's CSR, in place; xy: the keypoints of every frame as adjust() takes them; params: fields of
+        vslam_track_params over its defaults.  Returns (status (tracks, map_capacity) i32 or None, stats (tracks, 4) i32: points
+        taking part, OK, low parallax, other refusals), cuda tensors."""
+        import numpy as np
+        torch = self.ctx.torch
+        self.ctx._dev(xy, torch.float32, "xy")
+        xy_frames = xy.numel() // (self.tracks * self.kp_stride * 2)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.zeros((self.tracks, 4), dtype=torch.int32, device=xy.device)
+        status = torch.zeros((self.tracks, pmap.map_capacity), dtype=torch.int32, device=xy.device) if want_status else None
+        prm = TrackParams.make(self.lib, **params)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_retriangulate(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), C.c_int(xy_frames),
+                                                           Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(status), _ptr(stats)))
+        return status, stats
 
     def observations(self, pmap, desc=True):
         """vslam_world_observations (include/vslam_fuse.h): the CSR of the map's observations as this world sees it -- merged once a

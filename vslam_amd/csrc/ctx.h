@@ -417,6 +417,9 @@ int vs_world_search_writeback(vslam_ctx *ctx, vslam_world *world, int f1, double
 // given); with one, the map's lists fused with d_mask = d_fuse_to (include/vslam_fuse.h) and the descriptors gathered through
 // d_out_src.
 int vs_world_csr(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int32_t *off, int32_t *frame, int32_t *kp, uint8_t *desc);
+// camera f = recorded frame f of every track, from d_Twc as include/vslam_adjust.h forms "camera c" (fuse.hip's world_cameras_kernel):
+// R [tracks][max_frames][9], T [tracks][max_frames][3], n_cams [tracks] = frames
+int vs_world_cameras(vslam_ctx *ctx, vslam_world *world, int max_frames, int frames, double *R, double *T, int32_t *n_cams);
 int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world);   // "no fusion": d_fuse_to (if made) the identity
 struct vslam_match_params;   // include/vslam_pnp.h
 bool vs_match_params_ok(const vslam_match_params &p);   // search.hip

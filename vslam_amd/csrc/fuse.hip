@@ -14,7 +14,7 @@
 //   on the world (vslam_world_fuse, vslam_world_cull, vslam_world_observations and vs_world_csr, the helper through which every world
 //   call obtains its CSR): fuse_identity_kernel (d_fuse_to = "no fusion"), fuse_gather_desc_kernel (the merged rows' descriptors
 //   through d_out_src), world_fuse_apply_kernel (the new d_fuse_to, NaN rows for the newly absorbed), world_cameras_kernel (camera f =
-//   recorded frame f from d_Twc), world_cull_apply_kernel (-1 and a NaN row for the culled, -1 for the members of a culled survivor).
+//   recorded frame f from d_Twc; vs_world_cameras is its launch for tracks.hip too), world_cull_apply_kernel (-1 and a NaN row for the culled, -1 for the members of a culled survivor).
 // Words that one lane writes and another reads inside the fusion (labels, cells, running counts, row starts) move by relaxed
 // device-scope atomic loads and stores, which do not stay in a lane's nearest cache; barriers order them.  Integers only there; no
 // floating-point atomics and no scratch anywhere.
@@ -408,6 +408,12 @@ int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world) {
     return VSLAM_OK;
 }
 
+int vs_world_cameras(vslam_ctx *ctx, vslam_world *world, int max_frames, int frames, double *R, double *T, int32_t *n_cams) {
+    world_cameras_kernel<<<world->tracks, kFT, 0, ctx->stream>>>(world->Twc, max_frames, frames, R, T, n_cams);
+    VS_HIP(ctx, hipGetLastError());
+    return VSLAM_OK;
+}
+
 int vs_world_csr(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int32_t *off, int32_t *frame, int32_t *kp, uint8_t *desc) {
     int rc;
     if (!(world->fusion & 1)) {   // no fusion: the map's own lists, by the map's own launches
@@ -527,8 +533,7 @@ int vslam_world_cull(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const f
     if ((rc = vs_arena_get(ctx, "world_cull_f64", sizeof(double) * T * Fr * 12, &ptr))) return rc;
     double *R = static_cast<double *>(ptr), *Tv = R + T * Fr * 9;
     if ((rc = vs_world_csr(ctx, world, map, off, frame, kp, nullptr))) return rc;
-    world_cameras_kernel<<<m.tracks, kFT, 0, ctx->stream>>>(world->Twc, m.max_frames, m.frames, R, Tv, n_cams);
-    VS_HIP(ctx, hipGetLastError());
+    if ((rc = vs_world_cameras(ctx, world, m.max_frames, m.frames, R, Tv, n_cams))) return rc;
     CullArgs a;
     a.points = reinterpret_cast<const float4 *>(world->world_points); a.n_points = static_cast<const int32_t *>(m.d_sizes); a.pt_stride = m.map_capacity;
     a.off = off; a.cam = frame; a.kp = kp; a.obs_stride = m.obs_capacity;

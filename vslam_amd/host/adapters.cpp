@@ -919,6 +919,19 @@ void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, i
                                      cam_stride, d_xy, kp_stride, k, batch, params, d_keep, d_counts, d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_cull_points: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+void triangulate_tracks(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets,
+                        const s32 *d_obs_cam, const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams,
+                        int cam_stride, const float *d_xy, int kp_stride, const cv::Mat &K, int batch, float *d_out_points, s32 *d_status,
+                        s32 *d_stats, s32 *d_counts, f64 *d_info, const vslam_track_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("triangulate_tracks: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_triangulate_tracks(ctx, d_points, d_n_points, pt_stride, d_obs_offsets, d_obs_cam, d_obs_kp, obs_stride, d_R, d_T,
+                                            d_n_cams, cam_stride, d_xy, kp_stride, k, batch, params, d_out_points, d_status, d_counts, d_info,
+                                            d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_triangulate_tracks: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
