@@ -507,6 +507,8 @@ __global__ __launch_bounds__(kRankThreads) void ransac_rank_kernel(
 #else
 #define VS_SCREEN_ROUTE_PARAM
 #endif
+// kRows (experiments build only, VSLAM_RANSAC_PRUNE_ROWS): the head path in the row-per-hypothesis form it had before.
+template <bool kRows>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void ransac_screen_kernel(
     const float *__restrict__ rk, int kp_pad, const int32_t *__restrict__ m_arr, int min_m, int kp_stride, int hyp,
     float threshold, const float *__restrict__ hypF, const float *__restrict__ cmax, const int32_t *__restrict__ cbound,
@@ -523,13 +525,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     if (m < min_m) return;
     // The pair's head on the prune certificate instead (workgroup-uniform; the same 4 waves x 32 hypotheses).  One kernel with
     // this branch, not a launch of its own: a launch whose 8192 workgroups all return costs 0.006 to 0.012 ms
-    // (profiles/r09_matrix_pipe_ab.txt section 3).  Either path alone compiles to 68 vector registers; together the compiler
-    // took 108 (four waves per SIMD), and amdgpu_waves_per_eu(7, 7) above holds the kernel to 72 without a spill (section 4).
+    // (profiles/r09_matrix_pipe_ab.txt section 3).  amdgpu_waves_per_eu(7, 7) above holds the two paths together to 72 vector
+    // registers without a spill; left to itself the compiler takes 79 (six waves per SIMD) with the head counted in the lanes
+    // (profiles/r10_prune_lanes_ab.txt section 1), and took 108 with the row-per-hypothesis head of round 9.
     if (vs_head_on_certificate(m, bound_pilots, min(m, kScreenMatches), route)) {
         static_assert(kScreenHyps == vs_prune::kPruneWaves * vs_prune::kPruneHyps && kScreenMatches <= vs_prune::kHeadTiles * vs_prune::kPruneTile,
                       "a wave of the screen is a wave of the prune tile");
-        if (hbase + wave * 32 < hyp)   // wave-uniform
-            vs_prune::head_on_certificate(rk, kp_pad, b, m, min(m, kScreenMatches), hbase + wave * 32, hyp, threshold, splus, hypF, cmax, pot0, head);
+        if (hbase + wave * 32 < hyp) {   // wave-uniform
+#ifdef VSLAM_EXPERIMENTS
+            if constexpr (kRows)
+                vs_prune::head_on_certificate_rows(rk, kp_pad, b, m, min(m, kScreenMatches), hbase + wave * 32, hyp, threshold, splus, hypF, cmax, pot0, head);
+            else
+#endif
+                vs_prune::head_on_certificate(rk, kp_pad, b, m, min(m, kScreenMatches), hbase + wave * 32, hyp, threshold, splus, hypF, cmax, pot0, head);
+        }
         return;
     }
     __shared__ __align__(16) float s_rec[kScreenHyps * kCntRec];
@@ -1066,11 +1075,15 @@ int vs_launch_ransac_count(vslam_ctx *ctx, const float *xy1, const float *xy2, c
         VsProfScope ps(ctx, "ransac_screen_kernel");
         dim3 grid(vs_div_up(hyp, kScreenHyps), batch);
 #ifdef VSLAM_EXPERIMENTS
-        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
-                                                            pc_splus(threshold), route, route_out);
+        if (vs_prune_rows_form())
+            ransac_screen_kernel<true><<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
+                                                                      pc_splus(threshold), route, route_out);
+        else
+            ransac_screen_kernel<false><<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
+                                                                       pc_splus(threshold), route, route_out);
 #else
-        ransac_screen_kernel<<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
-                                                            pc_splus(threshold), route);
+        ransac_screen_kernel<false><<<grid, 256, 0, ctx->stream>>>(rk, kp_pad, m, min_m, kp_stride, hyp, threshold, hypF, cmax, cbound, pot0, head,
+                                                                   pc_splus(threshold), route);
 #endif
     }
 #ifdef VSLAM_EXPERIMENTS   // pot0 as the screen leaves it, before ransac_prune marks the dead
