@@ -22,16 +22,21 @@ using namespace vs_ransac;
 // 72 floats per lane in LDS held the kernel at 8 waves per CU (2 per SIMD); it is bound by dependent f64 chains on the
 // vector pipe, where more waves pay (2 -> 3 per SIMD: 0.96 -> 0.88 ms with three of the rows in registers).  With all
 // eight rows in registers (72 VGPRs; every (i, j) step written out, the row indices compile-time) the sweeps touch no
-// LDS at all, 128 VGPRs suffice and 4 waves fit.  Only the part after the sweeps wants rows by run-time index: rows
-// 0..3 go to LDS for it (36 floats per lane).  Every operation on every value is the one
-// jacobi_svd_lanes<9, 8, 9, false> (the plain restatement in ransac_svd.h) would perform, in the same order.
-constexpr int kSolveLdsRows = 4;
-constexpr int kSolveSplitFloats = kSolveLdsRows * 9;
+// LDS at all, 128 VGPRs suffice and 4 waves fit.  The part after the sweeps sorts the rows in place, between compile-time
+// positions, so it needs no LDS either; the kernel's LDS is the 3 x 3 solve's (18 floats per lane).  Every operation on
+// every value is the one jacobi_svd_lanes<9, 8, 9, false> (the plain restatement in ransac_svd.h) would perform, in the
+// same order.
+// Where the kernel's values live is decided as much by what surrounds the arithmetic as by the arithmetic: c and s of
+// jacobi_cs_full coming back through pointers, and the rare closing path as the other side of an if / else, each put
+// values of the common path into scratch memory (363 spilled registers, one row element going through memory on every
+// rotation).  Both are written below so that nothing of the common path is live across a call.
+constexpr int kSolveLdsFloats = 18;
 
 // c, s of a rotation for operands outside the range the short sqrt / division sequences cover (see jacobi_svd_lanes).
 // Deliberately a real call: it is reached by a wave-wide vote that practically never passes, and 28 inlined copies of the
-// IEEE sqrt and division expansions would double the size of the sweep loop.
-__device__ __attribute__((noinline)) void jacobi_cs_full(double p, double beta, double g2, float *c_out, float *s_out) {
+// IEEE sqrt and division expansions would double the size of the sweep loop.  (c, s) come back in registers: returned
+// through pointers they are two stack objects, and the sweep loop addresses scratch memory around every call site.
+__device__ __attribute__((noinline)) float2 jacobi_cs_full(double p, double beta, double g2) {
     float c, s;
     const double gamma = sqrt(g2);   // pinned hypot
     if (beta < 0) {
@@ -42,8 +47,7 @@ __device__ __attribute__((noinline)) void jacobi_cs_full(double p, double beta, 
         c = (float)sqrt((gamma + beta) / (gamma * 2));
         s = (float)(p / (gamma * (double)c * 2));
     }
-    *c_out = c;
-    *s_out = s;
+    return make_float2(c, s);
 }
 
 // one (i, j) step on two rows held in registers.  Returns whether this lane rotated (the rows are then the rotated ones).
@@ -76,7 +80,9 @@ __device__ __forceinline__ bool jacobi_pair_9(float (&ai)[9], float (&aj)[9]) {
         s = neg ? first : second;
         c = neg ? second : first;
     } else {
-        jacobi_cs_full(p, beta, g2, &c, &s);
+        const float2 cs = jacobi_cs_full(p, beta, g2);
+        c = cs.x;
+        s = cs.y;
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) {
@@ -103,72 +109,110 @@ __device__ __forceinline__ bool jacobi_sweep_8x9_regs(float (&R)[8][9]) {
     return changed;
 }
 
+// The rare form of the part after the sweeps: jacobi_finish on a private copy of the rows (see jacobi_null_row_8x9).  A real
+// call, like jacobi_cs_full: its loops over run-time rows stay out of the kernel's register allocation.  The result comes
+// back in registers, so the caller's f0 is no stack object.
+struct NullRow {
+    float f[9];
+};
+__device__ __attribute__((noinline)) NullRow jacobi_null_row_private(float *rows) {
+    NullRow out;
+    float w8[8];
+    jacobi_finish<9, 8, 9, false, 1>(rows, nullptr, w8, out.f);
+    return out;
+}
+
 // After the sweeps: V_t.row(8) of SVDecomp(A 8x9, FULL_UV) = the row beyond the rank, orthogonalised against the sorted,
 // normalised rows (jacobi_finish<9, 8, 9, false, .> with only extra_row kept).  If a row's norm does not exceed FLT_MIN
-// OpenCV regenerates that row from its RNG stream first (degenerate samples): any lane in that case sends the wave
-// through jacobi_finish itself on a private copy.  Otherwise a row's normalisation factor is a function of that row alone
-// and the sort only fixes the ORDER in which the rows are visited, so nothing has to move: rowid[ii] = the row at sorted
-// position ii.  Rows below kSolveLdsRows are parked in LDS (pA = this lane's column, element (r, k) at
-// pA[(9 r + k) * 64]) so that a run-time row id is an address; the others are picked with selects.
-__device__ __forceinline__ void jacobi_null_row_8x9(float *pA, float (&R)[8][9], float *f0) {
-    constexpr int M = 9, N = 8, L = kSolveLdsRows;
+// OpenCV regenerates that row from its RNG stream first (degenerate samples): a wave with a lane that may be in that
+// case goes through jacobi_finish itself on a private copy.  Otherwise a row's normalisation factor is a function of that
+// row alone, so the rows are normalised where they are and then sorted: the selection sort's swap of rows i and j becomes
+// a conditional swap of row i with each row behind it (28 candidates, 18 selects each, once, and only in a wave where the
+// sort has anything to do), after which the orthogonalisation reads registers in static order.
+__device__ __forceinline__ void jacobi_null_row_8x9(float (&R)[8][9], float *f0) {
+    constexpr int M = 9, N = 8;
     const double minval = FLT_MIN;
     const float eps = FLT_EPSILON * 2;
+    // A row is tiny when its norm sqrt(sum of squares) <= FLT_MIN = 2^-126.  A row with an element of magnitude 2^-120 or
+    // more has a sum of squares of at least 2^-240 and is not tiny, so the vote below passes whenever a row is tiny.  It
+    // may pass for rows that are not: jacobi_finish is the general procedure and gives those the same bits.  Voting on the
+    // elements, before the norms exist, keeps the norms from being live across the call.
+    float small = 0x1p-120f;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        float big = fabsf(R[i][0]);
+#pragma unroll
+        for (int k = 1; k < M; k++) big = fmaxf(big, fabsf(R[i][k]));
+        small = fminf(small, big);
+    }
+    int usual = 1;
+    if (__any(small < 0x1p-120f)) {
+        float rows[N * M];
+#pragma unroll
+        for (int i = 0; i < N; i++)
+#pragma unroll
+            for (int k = 0; k < M; k++) rows[i * M + k] = R[i][k];
+        const NullRow nr = jacobi_null_row_private(rows);
+#pragma unroll
+        for (int k = 0; k < M; k++) f0[k] = nr.f[k];
+        // Not `return`: as the two sides of an if / else the paths are laid out one behind the other, every row counts as
+        // live through the call, and the usual path spills too.  As two ifs in sequence, the flag opaque to the compiler
+        // and the rows read back (they are never used), nothing is live across the call.
+#pragma unroll
+        for (int i = 0; i < N; i++)
+#pragma unroll
+            for (int k = 0; k < M; k++) R[i][k] = rows[i * M + k];
+        usual = 0;
+        asm volatile("" : "+s"(usual));
+    }
+    if (!usual) return;
     double W[N];
-    bool tiny = false;
 #pragma unroll
     for (int i = 0; i < N; i++) {
         double sd = 0;
 #pragma unroll
         for (int k = 0; k < M; k++) sd = __builtin_fma((double)R[i][k], (double)R[i][k], sd);
         W[i] = sqrt(sd);
-        tiny = tiny || W[i] <= minval;
     }
-    if (__any(tiny)) {
-        float rows[N * M], w8[N];
-#pragma unroll
-        for (int i = 0; i < N; i++)
-#pragma unroll
-            for (int k = 0; k < M; k++) rows[i * M + k] = R[i][k];
-        jacobi_finish<9, 8, 9, false, 1>(rows, nullptr, w8, f0);
-        return;
-    }
-    // normalise (row *= (float)(1 / W), W = the row's norm), park the first rows
+    // normalise (row *= (float)(1 / W), W = the row's norm)
 #pragma unroll
     for (int i = 0; i < N; i++) {
         const float s = (float)(1 / W[i]);
 #pragma unroll
-        for (int k = 0; k < M; k++) {
-            R[i][k] = R[i][k] * s;
-            if (i < L) pA[(i * 9 + k) * kSolveThreads] = R[i][k];
-        }
+        for (int k = 0; k < M; k++) R[i][k] = R[i][k] * s;
     }
-    // the descending selection sort, on (W, row id) pairs
-    int rowid[N];
+    // The descending selection sort.  A rotation leaves the larger norm in the row of the lower index, so the sweeps
+    // nearly always end with the rows in order already: the sort moves something exactly when W[i] < W[k] for some i < k
+    // (its first such i is where it first swaps), and only a wave with such a lane goes through it.  There the rows travel
+    // with W as conditional swaps between compile-time positions.
+    bool unsorted = false;
 #pragma unroll
-    for (int i = 0; i < N; i++) rowid[i] = i;
+    for (int i = 0; i < N - 1; i++)
 #pragma unroll
-    for (int i = 0; i < N - 1; i++) {
-        int j = i;
-        double wj = W[i];
+        for (int k = i + 1; k < N; k++) unsorted = unsorted || W[i] < W[k];
+    if (__any(unsorted)) {
 #pragma unroll
-        for (int k = i + 1; k < N; k++)
-            if (wj < W[k]) {
-                j = k;
-                wj = W[k];
-            }
-        if (i != j) {
-            const int ri = rowid[i];
-            int rj = ri;
+        for (int i = 0; i < N - 1; i++) {
+            int j = i;
+            double wj = W[i];
 #pragma unroll
-            for (int jj = i + 1; jj < N; jj++)
-                if (jj == j) {
-                    W[jj] = W[i];
-                    rj = rowid[jj];
-                    rowid[jj] = ri;
+            for (int k = i + 1; k < N; k++)
+                if (wj < W[k]) {
+                    j = k;
+                    wj = W[k];
                 }
+#pragma unroll
+            for (int jj = i + 1; jj < N; jj++) {
+                const bool hit = jj == j;
+                W[jj] = hit ? W[i] : W[jj];
+#pragma unroll
+                for (int k = 0; k < M; k++) {
+                    const float x = R[i][k], y = R[jj][k];
+                    R[i][k] = hit ? y : x;
+                    R[jj][k] = hit ? x : y;
+                }
+            }
             W[i] = wj;
-            rowid[i] = rj;
         }
     }
     // the row beyond the rank: jacobi_finish's N1 > N block, rows visited in sorted order
@@ -182,16 +226,11 @@ __device__ __forceinline__ void jacobi_null_row_8x9(float *pA, float (&R)[8][9],
         for (int iter = 0; iter < 2; iter++) {
 #pragma unroll
             for (int jj = 0; jj < N; jj++) {
-                const int r = rowid[jj];
-                const int rl = r < L ? r : 0;
                 float vj[M];
                 sd = 0;
 #pragma unroll
                 for (int k = 0; k < M; k++) {
-                    float t = pA[(rl * 9 + k) * kSolveThreads];
-#pragma unroll
-                    for (int q = L; q < N; q++) t = r == q ? R[q][k] : t;
-                    vj[k] = t;
+                    vj[k] = R[jj][k];
                     sd += (double)(v[k] * vj[k]);   // float product, double running sum
                 }
                 float asum = 0;
@@ -268,7 +307,7 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(W
     const int h = blockIdx.x * kSolveThreads + tid;
     if (m_arr[b] < min_m) return;   // uniform per workgroup (8 unless RansacFilter::min_items is smaller)
 
-    __shared__ float sA[kSolveSplitFloats * kSolveThreads];
+    __shared__ float sA[kSolveLdsFloats * kSolveThreads];   // fundamental_rank2's 9 + 9 columns per lane
 
     const bool live = h < hyp;
     const int hc = live ? h : hyp - 1;   // idle lanes redo the last hypothesis; no divergence in barriers
@@ -299,7 +338,7 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(W
         constexpr int max_iter = 30;
         for (int iter = 0; iter < max_iter; iter++)
             if (!jacobi_sweep_8x9_regs(R)) break;
-        jacobi_null_row_8x9(sA + tid, R, f0);
+        jacobi_null_row_8x9(R, f0);
     }
 
     float F[9];
