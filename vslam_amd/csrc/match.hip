@@ -398,6 +398,16 @@ __device__ __forceinline__ v4i spread32_pm1(uint32_t w) {       // 32 bits -> 32
     return r;
 }
 __device__ __forceinline__ float med3_f32(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
+// v_max_f32 on values that are never NaN (as max3_nonan of image_common.h).  fmaxf() must quiet a signalling NaN, and the
+// compiler cannot see through a loop-carried operand that there is none: it put a `v_max_f32 vN, vN, vN` in front of the
+// running maximum of every one of the 16 results of a lane, 16 of the tile loop's 122 vector instructions.  A key is
+// dot * 16384 - index with |dot| <= 256 an exact integer sum of +-1 products (E2M1 holds no NaN and no infinity) and the
+// index at most kFPad = 2^25: finite, |key| < 2^26; the start value kFNone is finite too.  Pure register instruction.
+__device__ __forceinline__ float max_nonan(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 // -v, 0 <= v <= 127, as 32 E2M1 nibbles that sum to it: v / 6 times -6.0 (0xF), then the remainder as -1.0 (0xA), -2.0 (0xC),
 // -3.0 (0xD), -4.0 (0xE) or -4.0 and -1.0; the rest +0.0.  At most 23 nibbles are used.
 __device__ __forceinline__ v4i index_chunk(int v) {
@@ -434,7 +444,9 @@ __global__ __launch_bounds__(256) void match_spread_kernel(const uint8_t *__rest
 
 // PRE: the train rows come spread already (tx, match_spread_kernel); otherwise the workgroup spreads them itself.
 // CT = train tiles per trip of the main loop (one barrier per trip; 2 only with PRE).
-template <int RT, bool PRE, int CT, int KF>
+// FMAX (experiments build, VSLAM_MATCH_MAX_FORM=fmaxf): the running maximum as fmaxf(), the form of rounds 4 to 11, for the bit
+// comparison and A/B timing.
+template <int RT, bool PRE, int CT, int KF, bool FMAX = false>
 __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
     const uint8_t *__restrict__ desc1, const int32_t *__restrict__ n1, const uint8_t *__restrict__ desc2,
     const int32_t *__restrict__ n2, int kp_stride, int32_t *__restrict__ sel, int32_t *__restrict__ knn,
@@ -613,7 +625,7 @@ __global__ __launch_bounds__(64 * kMQ / (32 * RT)) void match_knn2_fp4_kernel(
                     const float key = KF == 0 ? __builtin_fmaf(acc[c][rt][g], kFScale, nidx[c])
                                               : (KF == 1 ? acc[c][rt][g] + nidx[c] : acc[c][rt][g]);
                     k2[rt][g] = med3_f32(k1[rt][g], k2[rt][g], key);
-                    k1[rt][g] = fmaxf(k1[rt][g], key);
+                    k1[rt][g] = FMAX ? fmaxf(k1[rt][g], key) : max_nonan(k1[rt][g], key);
                 }
             }
         }
@@ -772,11 +784,17 @@ int vs_launch_match(vslam_ctx *ctx, const uint8_t *d1, const int32_t *n1, const 
                 const char *const kf_env = VS_EXPERIMENT_ENV("VSLAM_MATCH_KEY_FORM");
                 const int kf = kf_env ? atoi(kf_env) : kFKeyForm;
                 VS_REQUIRE(ctx, kf >= 0 && kf <= 3, VSLAM_ERR_INVALID);
-#define VS_FP4_LAUNCH(RT_, PRE_, CT_, KF_, THREADS_, TX_, PAD_) \
-    match_knn2_fp4_kernel<RT_, PRE_, CT_, KF_><<<xgrid, THREADS_, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, TX_, PAD_, batch, per_pair)
+                // VSLAM_MATCH_MAX_FORM=fmaxf (read at every call, as the key form): the running maximum as fmaxf(), with the
+                // quieting v_max_f32 per result that max_nonan spares.  Key form 0 (the product's) only.
+                const char *const mf_env = VS_EXPERIMENT_ENV("VSLAM_MATCH_MAX_FORM");
+                const bool fmax_form = mf_env && mf_env[0] == 'f';
+                VS_REQUIRE(ctx, !fmax_form || kf == 0, VSLAM_ERR_INVALID);
+#define VS_FP4_LAUNCH(RT_, PRE_, CT_, KF_, THREADS_, TX_, PAD_, ...) \
+    match_knn2_fp4_kernel<RT_, PRE_, CT_, KF_, ##__VA_ARGS__><<<xgrid, THREADS_, 0, ctx->stream>>>(d1, n1, d2, n2, kp_stride, sel, knn, TX_, PAD_, batch, per_pair)
 #define VS_FP4_FORMS(RT_, PRE_, CT_, THREADS_, TX_, PAD_)                                  \
     do {                                                                                   \
-        if (kf == 0) VS_FP4_LAUNCH(RT_, PRE_, CT_, 0, THREADS_, TX_, PAD_);                \
+        if (fmax_form) VS_FP4_LAUNCH(RT_, PRE_, CT_, 0, THREADS_, TX_, PAD_, true);        \
+        else if (kf == 0) VS_FP4_LAUNCH(RT_, PRE_, CT_, 0, THREADS_, TX_, PAD_);           \
         else if (kf == 3) VS_FP4_LAUNCH(RT_, PRE_, CT_, 3, THREADS_, TX_, PAD_);           \
         else if (kf == 2 && PRE_) VS_FP4_LAUNCH(RT_, PRE_, CT_, (PRE_ ? 2 : 1), THREADS_, TX_, PAD_); \
         else VS_FP4_LAUNCH(RT_, PRE_, CT_, 1, THREADS_, TX_, PAD_);                        \

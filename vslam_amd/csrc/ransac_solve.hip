@@ -51,6 +51,9 @@ __device__ __attribute__((noinline)) float2 jacobi_cs_full(double p, double beta
 }
 
 // one (i, j) step on two rows held in registers.  Returns whether this lane rotated (the rows are then the rotated ones).
+// TWOQ (experiments build, VSLAM_RANSAC_SOLVE_QUOTIENT=two): the first quotient's operands selected between the two branches'
+// own expressions, the form of round 11, for the bit comparison.
+template <bool TWOQ>
 __device__ __forceinline__ bool jacobi_pair_9(float (&ai)[9], float (&aj)[9]) {
     double a = 0, p = 0, b = 0;
 #pragma unroll
@@ -69,12 +72,23 @@ __device__ __forceinline__ bool jacobi_pair_9(float (&ai)[9], float (&aj)[9]) {
     const bool safe = g2 > 0x1p-400 && g2 < 0x1p400 && fabs(p) > 0x1p-300;
     if (!__any(!safe)) {
         // One instruction stream for both signs of beta (lanes of a wave differ in it, so as two branches both would run):
-        // the first of (c, s) is a square root of a quotient, the second a quotient by it; which is which, and the operands
-        // of the first quotient, are selected.  The operations on every lane are the ones its branch would perform.
+        // the first of (c, s) is a square root of a quotient, the second a quotient by it; which is which is
+        // selected.  The first quotient is one expression for both signs, with the bits each branch would give:
+        //   beta < 0:   ((gamma - beta) * 0.5) / gamma.  gamma - beta is the IEEE operation gamma + |beta| (x - y = x + (-y), and
+        //               -beta = |beta| here), so the numerator is the expression below as written.
+        //   beta >= 0:  (gamma + beta) / (gamma * 2), with t = gamma + beta = gamma + |beta| (beta = -0 included: gamma > 0, and
+        //               gamma + 0 = gamma under either sign).  t * 0.5 and gamma * 2 are exact: the vote confines g2 to
+        //               (2^-400, 2^400), so gamma lies in [2^-200, 2^200] and t in [gamma, 2 gamma + ulp] -- no overflow, nothing
+        //               subnormal.  div_inrange(t * 0.5, gamma) and div_inrange(t, gamma * 2) then run the same sequence on
+        //               operands that differ by exact powers of two (v_rcp_f64 of 2 y is half that of y, every product and
+        //               fma of the corrections scales with it, all far from the exponent range's ends): the same quotient
+        //               bits, the rounding of t / (2 gamma) in [1/2, 1].
+        // |beta| is a source modifier of the add: this spares a subtraction, a multiplication and two f64 selects (four
+        // v_cndmask_b32) per visit, two of them on the dependent chain.  jacobi_cs_full above stays the reference sequence.
         const double gamma = sqrt_inrange(g2);   // pinned hypot
         const bool neg = beta < 0;
-        const double num = neg ? (gamma - beta) * 0.5 : gamma + beta;
-        const double den = neg ? gamma : gamma * 2;
+        const double num = TWOQ ? (neg ? (gamma - beta) * 0.5 : gamma + beta) : (gamma + fabs(beta)) * 0.5;
+        const double den = TWOQ ? (neg ? gamma : gamma * 2) : gamma;
         const float first = (float)sqrt_inrange(div_inrange(num, den));
         const float second = (float)div_inrange(p, gamma * (double)first * 2);
         s = neg ? first : second;
@@ -100,12 +114,13 @@ __device__ __forceinline__ bool jacobi_pair_9(float (&ai)[9], float (&aj)[9]) {
 // 13 KB instead of 40 KB: bit-identical, and 0.92 ms instead of 0.75.  The waits are the dependent f64 chains of a
 // rotation's parameters — two square roots and two divisions in sequence, about a hundred dependent instructions with
 // four waves per SIMD to hide them — not instruction fetch.)
+template <bool TWOQ>
 __device__ __forceinline__ bool jacobi_sweep_8x9_regs(float (&R)[8][9]) {
     bool changed = false;
 #pragma unroll
     for (int i = 0; i < 7; i++)
 #pragma unroll
-        for (int j = i + 1; j < 8; j++) changed |= jacobi_pair_9(R[i], R[j]);
+        for (int j = i + 1; j < 8; j++) changed |= jacobi_pair_9<TWOQ>(R[i], R[j]);
     return changed;
 }
 
@@ -298,7 +313,7 @@ __device__ __forceinline__ void fundamental_rank2(const float (&f0)[9], float *s
 // One lane per hypothesis, one wave per workgroup.  grid = (ceil(hyp / 64), batch).
 // SPLIT (round 5, VSLAM_RANSAC_SOLVE_SPLIT): the kernel stops behind the first SVD and leaves F0 = V_t.row(8) in hypF;
 // ransac_close_kernel turns it into F in place.  WPE: waves per SIMD the register budget is cut for.
-template <bool SPLIT, int WPE>
+template <bool SPLIT, int WPE, bool TWOQ = false>
 __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void ransac_solve_kernel(
     const float *__restrict__ xy1, const float *__restrict__ xy2, const int32_t *__restrict__ pairs,
     const int32_t *__restrict__ m_arr, int min_m, const int32_t *__restrict__ sets, int kp_stride, int hyp,
@@ -337,7 +352,7 @@ __global__ __launch_bounds__(kSolveThreads) __attribute__((amdgpu_waves_per_eu(W
     {   // SVDecomp(A 8x9), :94; f0 = V_t.row(8), :95
         constexpr int max_iter = 30;
         for (int iter = 0; iter < max_iter; iter++)
-            if (!jacobi_sweep_8x9_regs(R)) break;
+            if (!jacobi_sweep_8x9_regs<TWOQ>(R)) break;
         jacobi_null_row_8x9(R, f0);
     }
 
@@ -637,7 +652,11 @@ int vs_launch_ransac_solve(vslam_ctx *ctx, const float *xy1, const float *xy2, c
     ransac_solve_kernel<false, 4><<<grid, kSolveThreads, 0, ctx->stream>>>(xy1, xy2, pairs, m, ctx->ransac_min_matches, sets, kp_stride, hyp, hypF);
 #else
     const int split = ctx->solve_split;
-    if (split == 0) {
+    // VSLAM_RANSAC_SOLVE_QUOTIENT=two (read at every call: a test switches it within a process): jacobi_pair_9<true>
+    const char *const q_env = VS_EXPERIMENT_ENV("VSLAM_RANSAC_SOLVE_QUOTIENT");
+    if (split == 0 && q_env && q_env[0] == 't') {
+        ransac_solve_kernel<false, 4, true><<<grid, kSolveThreads, 0, ctx->stream>>>(xy1, xy2, pairs, m, ctx->ransac_min_matches, sets, kp_stride, hyp, hypF);
+    } else if (split == 0) {
         ransac_solve_kernel<false, 4><<<grid, kSolveThreads, 0, ctx->stream>>>(xy1, xy2, pairs, m, ctx->ransac_min_matches, sets, kp_stride, hyp, hypF);
     } else {
         if (split == 5)
