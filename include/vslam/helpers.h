@@ -12,6 +12,7 @@
 #include "../vslam_pnp.h"
 #include "../vslam_fuse.h"
 #include "../vslam_tracks.h"
+#include "../vslam_places.h"
 #include "Frame.h"
 #include "cvlite.h"
 #include "vslam_internal.h"
@@ -124,6 +125,39 @@ void triangulate_tracks(vslam_ctx *ctx, const float *d_points, const s32 *d_n_po
                         const s32 *d_obs_cam, const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams,
                         int cam_stride, const float *d_xy, int kp_stride, const cv::Mat &K, int batch, float *d_out_points, s32 *d_status,
                         s32 *d_stats, s32 *d_counts = nullptr, f64 *d_info = nullptr, const vslam_track_params *params = nullptr);
+
+// The nearest word of a vocabulary for every descriptor of a batch of frames the caller holds on the device (vslam_places_assign,
+// include/vslam_places.h: the arrays and strides are that call's).  d_dist may be nullptr.  Stream-ordered on `ctx`; throws
+// std::runtime_error with vslam_last_error.
+void places_assign(vslam_ctx *ctx, const unsigned char *d_desc, const s32 *d_n, int kp_stride, int frames, const unsigned char *d_vocab,
+                   int n_words, s32 *d_word, s32 *d_dist = nullptr);
+
+// A vocabulary of n_words words by k-majority from n descriptors (vslam_places_train, include/vslam_places.h).  Stream-ordered on
+// `ctx`; throws std::runtime_error with vslam_last_error.
+void places_train(vslam_ctx *ctx, const unsigned char *d_desc, int n, int n_words, int iterations, unsigned char *d_vocab, s32 *d_sizes);
+
+// A vslam_places (include/vslam_places.h: an index of frames as bags of binary words) held for a scope: made by the constructor,
+// destroyed with the object, which must go before its context.  Every member is that header's call of the same name on device
+// arrays, stream-ordered on the context, and throws std::runtime_error with vslam_last_error.  Not copyable.
+class Places {
+public:
+    Places(vslam_ctx *ctx, int n_words, int capacity, int max_kp);
+    ~Places();
+    Places(const Places &) = delete;
+    Places &operator=(const Places &) = delete;
+    void reset();
+    void set_vocabulary(const unsigned char *d_vocab, const s32 *d_weights = nullptr);
+    void set_weights(const s32 *d_weights);
+    void add(const unsigned char *d_desc, const s32 *d_n, int kp_stride, int frames, const s32 *d_tags, s32 *d_ids);
+    void query(const unsigned char *d_desc, const s32 *d_n, int kp_stride, int queries, const s32 *d_below, int top_k, s32 *d_best_id,
+               s32 *d_best_score, s32 *d_best_den, s32 *d_q_norm);
+    vslam_places_arrays view();
+    vslam_places *handle() const { return idx_; }
+
+private:
+    vslam_ctx *ctx_;
+    vslam_places *idx_ = nullptr;
+};
 
 // The map-association block of the capture loop (src/vslam.cpp:129-161 with orb_distance, src/PointMap.cpp:36-46) in one
 // device call -- what radius_search_batch is to a single radius_search.  map_points: N x 4 CV_32F rows (x, y, z, 1)

@@ -127,6 +127,29 @@ class TrackParams(_Params):
                 ("min_good", C.c_int32), ("good10", C.c_int32)]
 
 
+# every symbol include/vslam_places.h declares (a header of its own; tests/test_gpu_places.py checks it)
+PLACES_SYMBOLS = ["vslam_places_assign", "vslam_places_train", "vslam_places_create", "vslam_places_destroy", "vslam_places_reset",
+                  "vslam_places_set_vocabulary", "vslam_places_set_weights", "vslam_places_add", "vslam_places_query", "vslam_places_view"]
+PLACES_MAX_WORDS = 16384
+
+
+class PlacesArrays(C.Structure):   # vslam_places_arrays
+    _fields_ = [("n_words", C.c_int32), ("capacity", C.c_int32), ("max_kp", C.c_int32), ("size", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("d_offsets", "d_words", "d_tf", "d_df", "d_norms", "d_tags", "d_weights", "d_vocab")]
+
+
+def places_weights(df, n_entries):
+    """The rounded-log weights of an index: rint(1024 ln(n_entries / df)) where df > 0, else 0, clipped to 65535, int32.  Computed
+    HERE, on the host in float64, and nowhere else: the device never takes a logarithm, so the weights are an input to both sides
+    of every comparison."""
+    import numpy as np
+    df = np.asarray(df, np.int64)
+    w = np.zeros(df.shape, np.float64)
+    pos = df > 0
+    w[pos] = np.rint(1024.0 * np.log(np.float64(n_entries) / df[pos].astype(np.float64)))
+    return np.clip(w, 0, 65535).astype(np.int32)
+
+
 class ExtractParams(C.Structure):
     _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double),
                 ("cos_a", C.c_float), ("sin_a", C.c_float), ("d_pattern", C.c_void_p)]
@@ -704,6 +727,33 @@ class Context:
             self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), C.c_int(O), _ptr(R), _ptr(T),
             _ptr(n_cams), C.c_int(Cs), _ptr(xy), C.c_int(Kp), Kh.ctypes.data_as(C.c_void_p), C.c_int(B), C.byref(prm), _ptr(o["out_points"]),
             _ptr(o["status"]), _ptr(o.get("counts")), _ptr(o.get("info")), _ptr(o["stats"])))
+        return o
+
+    def places_assign(self, desc, n, vocab, out=None, want_dist=True):
+        """vslam_places_assign (include/vslam_places.h): the nearest word of vocab (W, 32) u8 for every descriptor of desc
+        (frames, kp_stride, 32) u8, n (frames,) i32 of them per frame.  Returns a dict: word, dist (want_dist) (frames, kp_stride) i32."""
+        torch = self.torch
+        Fr, Kp, W = desc.shape[0], desc.shape[1], vocab.shape[0]
+        for x, dt, nm in ((desc, torch.uint8, "desc"), (n, torch.int32, "n"), (vocab, torch.uint8, "vocab")):
+            self._dev(x, dt, nm)
+        shapes = dict(word=((Fr, Kp), torch.int32))
+        if want_dist:
+            shapes.update(dist=((Fr, Kp), torch.int32))
+        o = self._outputs(out, shapes, desc.device)
+        self._ready()
+        self._check(self.lib.vslam_places_assign(self.handle, _ptr(desc), _ptr(n), C.c_int(Kp), C.c_int(Fr), _ptr(vocab), C.c_int(W),
+                                                 _ptr(o["word"]), _ptr(o.get("dist"))))
+        return o
+
+    def places_train(self, desc, n_words, iterations=4, out=None):
+        """vslam_places_train (include/vslam_places.h): a vocabulary of n_words by k-majority from desc (n, 32) u8.  Returns a dict:
+        vocab (n_words, 32) u8, sizes (n_words,) i32."""
+        torch = self.torch
+        self._dev(desc, torch.uint8, "desc")
+        o = self._outputs(out, dict(vocab=((max(n_words, 0), 32), torch.uint8), sizes=((max(n_words, 0),), torch.int32)), desc.device)
+        self._ready()
+        self._check(self.lib.vslam_places_train(self.handle, _ptr(desc), C.c_int(desc.shape[0]), C.c_int(n_words), C.c_int(iterations),
+                                                _ptr(o["vocab"]), _ptr(o["sizes"])))
         return o
 
     def kdtree_build(self, xy, n):
@@ -1428,6 +1478,96 @@ class World:
         if self.handle:
             if self.ctx.handle:
                 self.lib.vslam_world_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Places:
+    """A vslam_places (include/vslam_places.h): an index of frames as bags of binary words, queried for the entries that look like a
+    frame.  tests/ref_places.py restates it."""
+
+    def __init__(self, ctx, n_words, capacity, max_kp):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.n_words, self.capacity, self.max_kp = n_words, capacity, max_kp
+        self.handle = C.c_void_p()
+        ctx._check(self.lib.vslam_places_create(ctx.handle, C.c_int(n_words), C.c_int(capacity), C.c_int(max_kp), C.byref(self.handle)))
+
+    def _i32(self, t, name):
+        return self.ctx._dev(t, self.ctx.torch.int32, name)
+
+    def reset(self):
+        self.ctx._check(self.lib.vslam_places_reset(self.ctx.handle, self.handle))
+
+    def set_vocabulary(self, vocab, weights=None):
+        """vocab (n_words, 32) u8; weights (n_words,) i32 or None (all 1).  Only while the index is empty."""
+        self.ctx._dev(vocab, self.ctx.torch.uint8, "vocab")
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_places_set_vocabulary(self.ctx.handle, self.handle, _ptr(vocab), _ptr(self._i32(weights, "weights"))))
+
+    def set_weights(self, weights=None):
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_places_set_weights(self.ctx.handle, self.handle, _ptr(self._i32(weights, "weights"))))
+
+    def add(self, desc, n, tags=None, out=None):
+        """desc (frames, kp_stride, 32) u8, n (frames,) i32, tags (frames, 2) i32 or None.  Returns the ids (frames,) i32."""
+        torch = self.ctx.torch
+        self.ctx._dev(desc, torch.uint8, "desc")
+        Fr, Kp = desc.shape[0], desc.shape[1]
+        ids = out if out is not None else torch.zeros((Fr,), dtype=torch.int32, device=desc.device)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_places_add(self.ctx.handle, self.handle, _ptr(desc), _ptr(self._i32(n, "n")), C.c_int(Kp), C.c_int(Fr),
+                                                  _ptr(self._i32(tags, "tags")), _ptr(self._i32(ids, "ids"))))
+        return ids
+
+    def query(self, desc, n, top_k=1, below=None, out=None):
+        """desc (queries, kp_stride, 32) u8, n (queries,) i32, below (queries,) i32 or None.  Returns a dict: best_id, best_score,
+        best_den (queries, top_k) i32 and q_norm (queries,) i32."""
+        torch = self.ctx.torch
+        self.ctx._dev(desc, torch.uint8, "desc")
+        Q, Kp, k = desc.shape[0], desc.shape[1], max(top_k, 0)
+        o = self.ctx._outputs(out, dict(best_id=((Q, k), torch.int32), best_score=((Q, k), torch.int32), best_den=((Q, k), torch.int32),
+                                        q_norm=((Q,), torch.int32)), desc.device)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_places_query(self.ctx.handle, self.handle, _ptr(desc), _ptr(self._i32(n, "n")), C.c_int(Kp), C.c_int(Q),
+                                                    _ptr(self._i32(below, "below")), C.c_int(top_k), _ptr(o["best_id"]), _ptr(o["best_score"]),
+                                                    _ptr(o["best_den"]), _ptr(o["q_norm"])))
+        return o
+
+    def arrays(self):
+        a = PlacesArrays()
+        self.ctx._check(self.lib.vslam_places_view(self.ctx.handle, self.handle, C.byref(a)))
+        return a
+
+    def view(self):
+        """Host copies (numpy) of the index, after waiting for the context's stream: size, offsets (size + 1,), words, tf (nnz,),
+        df (n_words,), norms (size,) under the current weights, tags (size, 2), weights (n_words,), vocab (n_words, 32)."""
+        import numpy as np
+        a = self.arrays()
+        self.ctx._check(self.lib.vslam_ctx_wait(self.ctx.handle))
+
+        def get(ptr, shape, dtype=np.int32):
+            h = np.empty(shape, dtype)
+            if h.nbytes:
+                self.ctx._check(self.lib.vslam_copy_d2h(self.ctx.handle, h.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(h.nbytes)))
+            return h
+        size, W = int(a.size), int(a.n_words)
+        offsets = get(a.d_offsets, (size + 1,))
+        nnz = int(offsets[size])
+        return dict(size=size, offsets=offsets, words=get(a.d_words, (nnz,)), tf=get(a.d_tf, (nnz,)), df=get(a.d_df, (W,)),
+                    norms=get(a.d_norms, (size,)), tags=get(a.d_tags, (size, 2)), weights=get(a.d_weights, (W,)),
+                    vocab=get(a.d_vocab, (W, 32), np.uint8))
+
+    def close(self):
+        """Before the context's close()."""
+        if self.handle:
+            if self.ctx.handle:
+                self.lib.vslam_places_destroy(self.ctx.handle, self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -932,6 +932,44 @@ void triangulate_tracks(vslam_ctx *ctx, const float *d_points, const s32 *d_n_po
                                             d_stats);
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_triangulate_tracks: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
+
+static void places_check(vslam_ctx *ctx, int rc, const char *what) {
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string(what) + ": " + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
+void places_assign(vslam_ctx *ctx, const unsigned char *d_desc, const s32 *d_n, int kp_stride, int frames, const unsigned char *d_vocab,
+                   int n_words, s32 *d_word, s32 *d_dist) {
+    places_check(ctx, vslam_places_assign(ctx, d_desc, d_n, kp_stride, frames, d_vocab, n_words, d_word, d_dist), "vslam_places_assign");
+}
+
+void places_train(vslam_ctx *ctx, const unsigned char *d_desc, int n, int n_words, int iterations, unsigned char *d_vocab, s32 *d_sizes) {
+    places_check(ctx, vslam_places_train(ctx, d_desc, n, n_words, iterations, d_vocab, d_sizes), "vslam_places_train");
+}
+
+Places::Places(vslam_ctx *ctx, int n_words, int capacity, int max_kp) : ctx_(ctx) {
+    places_check(ctx_, vslam_places_create(ctx_, n_words, capacity, max_kp, &idx_), "vslam_places_create");
+}
+Places::~Places() {
+    if (idx_) vslam_places_destroy(ctx_, idx_);
+}
+void Places::reset() { places_check(ctx_, vslam_places_reset(ctx_, idx_), "vslam_places_reset"); }
+void Places::set_vocabulary(const unsigned char *d_vocab, const s32 *d_weights) {
+    places_check(ctx_, vslam_places_set_vocabulary(ctx_, idx_, d_vocab, d_weights), "vslam_places_set_vocabulary");
+}
+void Places::set_weights(const s32 *d_weights) { places_check(ctx_, vslam_places_set_weights(ctx_, idx_, d_weights), "vslam_places_set_weights"); }
+void Places::add(const unsigned char *d_desc, const s32 *d_n, int kp_stride, int frames, const s32 *d_tags, s32 *d_ids) {
+    places_check(ctx_, vslam_places_add(ctx_, idx_, d_desc, d_n, kp_stride, frames, d_tags, d_ids), "vslam_places_add");
+}
+void Places::query(const unsigned char *d_desc, const s32 *d_n, int kp_stride, int queries, const s32 *d_below, int top_k, s32 *d_best_id,
+                   s32 *d_best_score, s32 *d_best_den, s32 *d_q_norm) {
+    places_check(ctx_, vslam_places_query(ctx_, idx_, d_desc, d_n, kp_stride, queries, d_below, top_k, d_best_id, d_best_score, d_best_den, d_q_norm),
+                 "vslam_places_query");
+}
+vslam_places_arrays Places::view() {
+    vslam_places_arrays a;
+    places_check(ctx_, vslam_places_view(ctx_, idx_, &a), "vslam_places_view");
+    return a;
+}
 }  // namespace vslam
 
 // -------------------------------------------------------------------------------------- optimizer.h
