@@ -7,7 +7,15 @@ its own minus `--gap` (more than `--gap` ids older than itself), with the rounde
 similarities, and the best one is verified the way the library leaves to its caller: the existing front end (match + RANSAC) runs on
 the pair (candidate, query) and the inlier count is printed.
 
-    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256]
+With --sim3 the similarity between the two frames' maps is printed as well (include/vslam_sim3.h).  Each of the two frames is
+triangulated against its neighbour in its own track (vslam_frontend_pairs_pose: points in that frame's camera coordinates, in the
+unit of that pair's baseline), the front end's inlier matches between candidate and query that have a point on both sides become
+3-D / 3-D correspondences, and Context.sim3_ransac relates them: B = s R A + t takes the candidate's little map to the query's.  s is
+the ratio of the two baselines, which nothing else in this file knows.  No polish: a revisit may share its camera centre with
+the candidate, where the polish cannot see the scale.  Expect "not found" often: two-view points over a short
+baseline are rough, and inlier_px (2 px, both ways) is untuned.
+
+    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256] [--sim3]
 """
 import argparse
 import os
@@ -20,12 +28,68 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vslam_amd import capi, synth  # noqa: E402
 
 
+def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev):
+    """{query: text}: for every query with a candidate, three pairs through vslam_frontend_pairs_pose -- (candidate, its neighbour),
+    (query, its neighbour), (candidate, query) -- then one batch of Context.sim3_ransac over what the three have in common"""
+    width, height, max_corners, hyp = sizes
+    cos_a, sin_a, pat = rot
+    K = np.array([[525, 0, width // 2], [0, 525, height // 2], [0, 0, 1]], np.float32)
+
+    def neighbour(f):   # the next frame of f's own track, the previous one for a track's last frame
+        return f + 1 if (f % a.frames) + 1 < a.frames else f - 1
+    cands = [int(best_id[q, 0]) for q in asked]
+    P = len(asked)
+    last = cands + list(asked) + cands
+    cur = [neighbour(c) for c in cands] + [neighbour(q) for q in asked] + list(asked)
+    both = torch.cat([bgr[last], bgr[cur]]).contiguous()
+    seeds = torch.arange(3 * P, dtype=torch.int32, device=dev)
+    o = ctx.frontend_pairs_pose(both, 3 * P, max_corners, cos_a, sin_a, pat, seeds, hyp, 10.0, K)
+    ctx.synchronize()
+    xy, matches, best, X = (o[k].cpu().numpy() for k in ("xy", "matches", "best", "points4d"))
+    S = max_corners
+    A, B = np.full((P, S, 3), np.nan), np.full((P, S, 3), np.nan)
+    xa, xb = np.full((P, S, 2), np.nan, np.float32), np.full((P, S, 2), np.nan, np.float32)
+    n = np.zeros(P, np.int32)
+
+    def points_of(pair):   # keypoint of the pair's first frame -> its point in that frame's camera coordinates
+        out = {}
+        for m in range(max(int(best[pair, 3]), 0) if best[pair, 0] >= 0 else 0):
+            p = X[pair, m].astype(np.float64)
+            if np.isfinite(p).all() and p[3] != 0 and p[2] / p[3] > 0:
+                out[int(matches[pair, m, 0])] = p[:3] / p[3]
+        return out
+    for i in range(P):
+        # the same image gives the same keypoints in every pair it takes part in: the extractor depends on the image alone
+        assert np.array_equal(xy[i], xy[2 * P + i]) and np.array_equal(xy[P + i], xy[3 * P + 2 * P + i])
+        pc, pq = points_of(i), points_of(P + i)
+        for m in range(max(int(best[2 * P + i, 3]), 0) if best[2 * P + i, 0] >= 0 else 0):
+            kc, kq = (int(v) for v in matches[2 * P + i, m])
+            if kc in pc and kq in pq:
+                A[i, n[i]], B[i, n[i]], xa[i, n[i]], xb[i, n[i]] = pc[kc], pq[kq], xy[i, kc], xy[P + i, kq]
+                n[i] += 1
+    t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    r = ctx.sim3_ransac(t(A), t(xa), t(B), t(xb), t(n), K, torch.arange(1, P + 1, dtype=torch.int32, device=dev), torch.zeros(P, **f64),
+                        torch.zeros((P, 9), **f64), torch.zeros((P, 3), **f64), hypotheses=256)
+    ctx.synchronize()
+    win, cnt, s, R, T = (r[k].cpu().numpy() for k in ("winner", "n_inliers", "scale", "R", "T"))
+    out = {}
+    for i, q in enumerate(asked):
+        if win[i] < 0:
+            out[q] = f"sim3: not found among {n[i]} 3-D pairs"
+        else:
+            ang = np.degrees(np.arccos(np.clip((np.trace(R[i].reshape(3, 3)) - 1) / 2, -1, 1)))
+            out[q] = f"sim3: s {s[i]:.3f}, turn {ang:.1f} deg, t ({T[i][0]:.2f}, {T[i][1]:.2f}, {T[i][2]:.2f}) from {cnt[i]} of {n[i]} 3-D pairs"
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tracks", type=int, default=3)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--gap", type=int, default=2)
     ap.add_argument("--words", type=int, default=256)
+    ap.add_argument("--sim3", action="store_true", help="print the similarity between the best candidate's map and the query's")
     a = ap.parse_args()
     width, height, max_corners, hyp, top_k = 320, 240, 1000, 256, 3
     dev = torch.device("cuda", 0)
@@ -64,11 +128,15 @@ def main():
         ctx.synchronize()
         inliers = dict(zip(asked, out["best"][:, 3].cpu().numpy().tolist()))
 
+    sim3 = similarities(ctx, a, bgr, asked, best_id, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev) if a.sim3 and asked else {}
+
     for q in range(N):
         cand = ", ".join(f"({tag[e][0]}, {tag[e][1]}) {s / d:.3f}" for e, s, d in zip(best_id[q], score[q], den[q]) if e >= 0)
         line = f"frame ({tag[q][0]}, {tag[q][1]}): " + (cand or "no candidate")
         if q in inliers:
             line += f"   -> best verified with {inliers[q]} inlier matches"
+        if q in sim3:
+            line += "; " + sim3[q]
         print(line)
     idx.close()
     ctx.close()

@@ -12,6 +12,7 @@
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
+#include "../vslam_sim3.h"
 #include "../vslam_fuse.h"
 #include "../vslam_tracks.h"
 
@@ -103,6 +104,27 @@ public:
         check(vslam_world_relocalise(ctx_, world_, map, d_xy_cur, d_desc_cur, d_n_cur, h_K, d_seeds, match, pnp, polish, d_found, d_winner,
                                      d_n_inliers, d_corr_point, d_corr_kp, d_n_corr, d_stats),
               "vslam_world_relocalise");
+    }
+    // The similarity between two recorded frames' maps for `items` pairs (track_a, frame_a, track_b, frame_b) (vslam_world_sim3,
+    // include/vslam_sim3.h: every array is that call's): the camera-to-camera model in d_scale / d_R / d_T and the world-to-world
+    // similarity X_a = s_w R_w X_b + t_w in d_s_w / d_R_w / d_t_w, both written where an item is found.  The world must be the one
+    // attached to `map`; nothing is written into either.  params / polish: nullptr for the defaults / no polish; d_point_a,
+    // d_point_b and d_stats may be nullptr.
+    void sim3(vslam_map *map, const int32_t *d_track_a, const int32_t *d_frame_a, const int32_t *d_track_b, const int32_t *d_frame_b, int items,
+              const int32_t *d_matches, const int32_t *d_n_matches, const float *d_xy_a, const float *d_xy_b, const float *h_K,
+              const uint32_t *d_seeds, double *d_scale, double *d_R, double *d_T, double *d_s_w, double *d_R_w, double *d_t_w, int32_t *d_found,
+              int32_t *d_n_corr, int32_t *d_n_inliers, int32_t *d_winner, int32_t *d_point_a = nullptr, int32_t *d_point_b = nullptr,
+              const vslam_resect_params *polish = nullptr, const vslam_sim3_params *params = nullptr, double *d_stats = nullptr) {
+        check(vslam_world_sim3(ctx_, world_, map, d_track_a, d_frame_a, d_track_b, d_frame_b, items, d_matches, d_n_matches, d_xy_a, d_xy_b, h_K,
+                               d_seeds, params, polish, d_scale, d_R, d_T, d_s_w, d_R_w, d_t_w, d_found, d_n_corr, d_n_inliers, d_winner,
+                               d_point_a, d_point_b, d_stats),
+              "vslam_world_sim3");
+    }
+    // Every listed track's world carried through X' = s R X + t (vslam_world_apply_sim3): h_track [items] on the HOST, distinct;
+    // d_s [items], d_R [items][9], d_t [items][3], d_apply [items] on the device.
+    void apply_sim3(vslam_map *map, const int32_t *h_track, const double *d_s, const double *d_R, const double *d_t, const int32_t *d_apply,
+                    int items) {
+        check(vslam_world_apply_sim3(ctx_, world_, map, h_track, d_s, d_R, d_t, d_apply, items), "vslam_world_apply_sim3");
     }
     // The map points of every track that share an observation fused into groups (vslam_world_fuse, include/vslam_fuse.h): the
     // world's d_fuse_to written, the rows of the newly absorbed points in d_world_points set to NaN.  The world must be the one

@@ -10,6 +10,7 @@
 #include "../vslam_adjust.h"
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
+#include "../vslam_sim3.h"
 #include "../vslam_fuse.h"
 #include "../vslam_tracks.h"
 #include "../vslam_places.h"
@@ -102,6 +103,21 @@ void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s3
                 const unsigned int *d_seeds, f64 *d_R, f64 *d_T, s32 *d_inlier, f64 *d_corr_points, float *d_corr_xy, s32 *d_corr_index,
                 s32 *d_n_inliers, s32 *d_winner, s32 *d_counts = nullptr, f64 *d_stats = nullptr, const vslam_pnp_params *params = nullptr,
                 const vslam_resect_params *polish = nullptr);
+
+// The similarity B = s R A + t between two views for a batch of items the caller holds on the device (vslam_sim3_ransac,
+// include/vslam_sim3.h: the arrays and strides are that call's): 3-point RANSAC over each item's 3-D / 3-D correspondences with
+// their keypoints in both images, d_scale / d_R / d_T written where an item is found.  K: 3 x 3 CV_32F, for both images; params:
+// nullptr for the defaults; polish: nullptr for none; d_corr_index, d_counts, d_stats may be nullptr.  Stream-ordered on `ctx`;
+// throws std::runtime_error with vslam_last_error.
+void sim3_ransac(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d_B, const float *d_xb, const s32 *d_n, int batch, int stride,
+                 const cv::Mat &K, const unsigned int *d_seeds, f64 *d_scale, f64 *d_R, f64 *d_T, s32 *d_inlier, s32 *d_corr_index,
+                 s32 *d_n_inliers, s32 *d_winner, s32 *d_counts = nullptr, f64 *d_stats = nullptr, const vslam_sim3_params *params = nullptr,
+                 const vslam_resect_params *polish = nullptr);
+// The 7-parameter polish alone (vslam_sim3_refine), d_scale / d_R / d_T in place over the correspondences i < n with d_mask[i] != 0
+// (nullptr: all of them); params: nullptr for the defaults; d_stats may be nullptr.
+void sim3_refine(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d_B, const float *d_xb, const s32 *d_n, int batch, int stride,
+                 const s32 *d_mask, const cv::Mat &K, f64 *d_scale, f64 *d_R, f64 *d_T, f64 *d_stats = nullptr,
+                 const vslam_resect_params *params = nullptr);
 
 // Map points that share an observation grouped, their observation lists merged, for a batch of items the caller holds on the
 // device (vslam_fuse_points, include/vslam_fuse.h: the arrays and strides are that call's).  d_mask, d_out_src and d_stats may be

@@ -106,6 +106,15 @@ class MatchParams(_Params):
     _fields_ = [("dist_threshold", C.c_int32), ("ratio10", C.c_int32)]
 
 
+# every symbol include/vslam_sim3.h declares (a header of its own; tests/test_sim3_lds.py checks it)
+SIM3_SYMBOLS = ["vslam_sim3_params_default", "vslam_sim3_ransac", "vslam_sim3_refine", "vslam_world_sim3", "vslam_world_apply_sim3"]
+
+
+class Sim3Params(_Params):
+    _struct = "vslam_sim3_params"
+    _fields_ = [("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("inlier_px", C.c_double)]
+
+
 # every symbol include/vslam_fuse.h declares (a header of its own; tests/test_gpu_fuse.py checks it)
 FUSE_SYMBOLS = ["vslam_cull_params_default", "vslam_fuse_points", "vslam_cull_points", "vslam_world_fuse", "vslam_world_cull",
                 "vslam_world_observations", "vslam_world_fusion_view"]
@@ -642,6 +651,60 @@ class Context:
             _ptr(o.get("corr_index")), _ptr(o["n_inliers"]), _ptr(o["winner"]), _ptr(o.get("counts")), _ptr(o.get("stats"))))
         o.update(R=R, T=T)
         return o
+
+    def sim3_ransac(self, A, xa, B, xb, n, K, seeds, scale, R, T, polish=None, out=None, want_index=True, want_counts=False,
+                    want_stats=True, **params):
+        """vslam_sim3_ransac (include/vslam_sim3.h): the similarity B = s R A + t of each item, from A, B (Bt, S, 3) f64 seen at xa,
+        xb (Bt, S, 2) f32, n (Bt,) i32 of them, seeds (Bt,) i32 / u32 bits; K: the 3 x 3 camera matrix of both images (host);
+        scale (Bt,), R (Bt, 9 or 3, 3) and T (Bt, 3) f64 are written IN PLACE where an item is found and keep their bits
+        elsewhere.  params: fields of vslam_sim3_params over its defaults; polish: None or a dict of vslam_resect_params fields
+        over their defaults.  out: a dict of output tensors to write into (missing ones are made, zero-filled).  Returns the
+        dict: scale, R, T; inlier (Bt, S) i32; corr_index (Bt, S) i32 (want_index); n_inliers, winner (Bt,) i32; counts
+        (Bt, hypotheses) i32 (want_counts); stats (Bt, 4) f64 (want_stats)."""
+        import numpy as np
+        torch = self.torch
+        Bt, S, _ = A.shape
+        for x, dt, nm in ((A, torch.float64, "A"), (xa, torch.float32, "xa"), (B, torch.float64, "B"), (xb, torch.float32, "xb"),
+                          (n, torch.int32, "n"), (seeds, torch.int32, "seeds"), (scale, torch.float64, "scale"), (R, torch.float64, "R"),
+                          (T, torch.float64, "T")):
+            self._dev(x, dt, nm)
+        prm = Sim3Params.make(self.lib, **params)
+        shapes = dict(inlier=((Bt, S), torch.int32), n_inliers=((Bt,), torch.int32), winner=((Bt,), torch.int32))
+        if want_index:
+            shapes.update(corr_index=((Bt, S), torch.int32))
+        if want_counts:
+            shapes.update(counts=((Bt, max(int(prm.hypotheses), 0)), torch.int32))
+        if want_stats:
+            shapes.update(stats=((Bt, 4), torch.float64))
+        o = self._outputs(out, shapes, A.device)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        pol = None if polish is None else ResectParams.make(self.lib, **polish)
+        self._ready()
+        self._check(self.lib.vslam_sim3_ransac(
+            self.handle, _ptr(A), _ptr(xa), _ptr(B), _ptr(xb), _ptr(n), C.c_int(Bt), C.c_int(S), Kh.ctypes.data_as(C.c_void_p), _ptr(seeds),
+            C.byref(prm), C.byref(pol) if pol is not None else C.c_void_p(0), _ptr(scale), _ptr(R), _ptr(T), _ptr(o["inlier"]),
+            _ptr(o.get("corr_index")), _ptr(o["n_inliers"]), _ptr(o["winner"]), _ptr(o.get("counts")), _ptr(o.get("stats"))))
+        o.update(scale=scale, R=R, T=T)
+        return o
+
+    def sim3_refine(self, A, xa, B, xb, n, K, scale, R, T, mask=None, want_stats=True, **params):
+        """vslam_sim3_refine (include/vslam_sim3.h): the 7-parameter polish of each item's scale (Bt,), R (Bt, 9 or 3, 3) and T
+        (Bt, 3) f64, IN PLACE, over the correspondences i < n with mask[i] != 0 (mask (Bt, S) i32 or None: all of them); params:
+        fields of vslam_resect_params over its defaults.  Returns (scale, R, T, stats (Bt, 4) f64 or None)."""
+        import numpy as np
+        torch = self.torch
+        Bt, S, _ = A.shape
+        for x, dt, nm in ((A, torch.float64, "A"), (xa, torch.float32, "xa"), (B, torch.float64, "B"), (xb, torch.float32, "xb"),
+                          (n, torch.int32, "n"), (mask, torch.int32, "mask"), (scale, torch.float64, "scale"), (R, torch.float64, "R"),
+                          (T, torch.float64, "T")):
+            self._dev(x, dt, nm)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.empty((Bt, 4), dtype=torch.float64, device=A.device) if want_stats else None
+        prm = ResectParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_sim3_refine(self.handle, _ptr(A), _ptr(xa), _ptr(B), _ptr(xb), _ptr(n), C.c_int(Bt), C.c_int(S), _ptr(mask),
+                                               Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(scale), _ptr(R), _ptr(T), _ptr(stats)))
+        return scale, R, T, stats
 
     def match_points(self, points, n_points, obs_offsets, obs_desc, xy, desc, n_kp, kp_taken=None, out=None, want_indices=True,
                      want_stats=True, **params):
@@ -1398,6 +1461,60 @@ class World:
             C.byref(mprm), C.byref(pprm), C.byref(rprm) if rprm is not None else C.c_void_p(0), _ptr(out["found"]), _ptr(out["winner"]),
             _ptr(out["n_inliers"]), _ptr(out["corr_point"]), _ptr(out["corr_kp"]), _ptr(out["n_corr"]), _ptr(out["stats"])))
         return out
+
+    def sim3(self, pmap, pairs, matches, n_matches, xy_a, xy_b, K, seeds=None, polish=None, want_points=True, **params):
+        """vslam_world_sim3 (include/vslam_sim3.h): the similarity between two recorded frames' maps for each row (track_a, frame_a,
+        track_b, frame_b) of pairs (items, 4) i32, from matches (items, kp_stride, 2) i32 / n_matches (items,) i32 as match_features
+        writes them (first: a keypoint of frame a) and the two frames' keypoints xy_a, xy_b (items, kp_stride, 2) f32.  This world
+        must be the one attached to `pmap`; nothing is written into either.  seeds: (items,) i32 bits, 1 .. items when None; polish:
+        None (the default: no polish -- it cannot see the scale when both frames share a camera centre) or a dict of
+        vslam_resect_params fields ({} the defaults); params: fields of vslam_sim3_params.  Returns a dict
+        of cuda tensors: scale (items,), R (items, 9), T (items, 3) f64 camera a -> camera b; s_w, R_w, t_w likewise, world b ->
+        world a (both written where found, zero elsewhere); found, n_corr, n_inliers, winner (items,) i32; point_a, point_b
+        (items, kp_stride) i32 (want_points); stats (items, 4) f64."""
+        import numpy as np
+        torch = self.ctx.torch
+        for x, dt, nm in ((pairs, torch.int32, "pairs"), (matches, torch.int32, "matches"), (n_matches, torch.int32, "n_matches"),
+                          (xy_a, torch.float32, "xy_a"), (xy_b, torch.float32, "xy_b")):
+            self.ctx._dev(x, dt, nm)
+        items = pairs.shape[0]
+        cols = [pairs[:, k].contiguous() for k in range(4)]
+        if seeds is None:
+            seeds = torch.arange(1, items + 1, dtype=torch.int32, device=pairs.device)
+        self.ctx._dev(seeds, torch.int32, "seeds")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        i32, f64 = dict(dtype=torch.int32, device=pairs.device), dict(dtype=torch.float64, device=pairs.device)
+        out = dict(scale=torch.zeros((items,), **f64), R=torch.zeros((items, 9), **f64), T=torch.zeros((items, 3), **f64),
+                   s_w=torch.zeros((items,), **f64), R_w=torch.zeros((items, 9), **f64), t_w=torch.zeros((items, 3), **f64),
+                   found=torch.zeros((items,), **i32), n_corr=torch.zeros((items,), **i32), n_inliers=torch.zeros((items,), **i32),
+                   winner=torch.zeros((items,), **i32), stats=torch.zeros((items, 4), **f64))
+        if want_points:
+            out.update(point_a=torch.full((items, self.kp_stride), -1, **i32), point_b=torch.full((items, self.kp_stride), -1, **i32))
+        prm = Sim3Params.make(self.lib, **params)
+        rprm = ResectParams.make(self.lib, **polish) if polish is not None else None
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_sim3(
+            self.ctx.handle, self.handle, pmap.handle, *(_ptr(c) for c in cols), C.c_int(items), _ptr(matches), _ptr(n_matches), _ptr(xy_a),
+            _ptr(xy_b), Kh.ctypes.data_as(C.c_void_p), _ptr(seeds), C.byref(prm), C.byref(rprm) if rprm is not None else C.c_void_p(0),
+            _ptr(out["scale"]), _ptr(out["R"]), _ptr(out["T"]), _ptr(out["s_w"]), _ptr(out["R_w"]), _ptr(out["t_w"]), _ptr(out["found"]),
+            _ptr(out["n_corr"]), _ptr(out["n_inliers"]), _ptr(out["winner"]), _ptr(out.get("point_a")), _ptr(out.get("point_b")),
+            _ptr(out["stats"])))
+        return out
+
+    def apply_sim3(self, pmap, tracks, s, R, t, apply=None):
+        """vslam_world_apply_sim3 (include/vslam_sim3.h): every listed track's world -- poses, scales, carry, world points --
+        carried through X' = s R X + t, in place.  tracks: a host sequence of distinct track indices; s (items,), R (items, 9), t
+        (items, 3) f64 and apply (items,) i32 (None: all ones) cuda tensors."""
+        import numpy as np
+        torch = self.ctx.torch
+        h = np.ascontiguousarray(np.asarray(tracks, np.int32).reshape(-1))
+        if apply is None:
+            apply = torch.ones((len(h),), dtype=torch.int32, device=s.device)
+        for x, dt, nm in ((s, torch.float64, "s"), (R, torch.float64, "R"), (t, torch.float64, "t"), (apply, torch.int32, "apply")):
+            self.ctx._dev(x, dt, nm)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_apply_sim3(self.ctx.handle, self.handle, pmap.handle, h.ctypes.data_as(C.c_void_p), _ptr(s), _ptr(R),
+                                                        _ptr(t), _ptr(apply), C.c_int(len(h))))
 
     def set_resection(self, enable=True, **params):
         """vslam_world_set_resection (include/vslam_resect.h), allowed at frame 0 only: from now on step() takes xy_cur and K

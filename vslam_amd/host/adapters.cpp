@@ -901,6 +901,27 @@ void pnp_ransac(vslam_ctx *ctx, const f64 *d_points, const float *d_xy, const s3
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_pnp_ransac: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
 
+void sim3_ransac(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d_B, const float *d_xb, const s32 *d_n, int batch, int stride,
+                 const cv::Mat &K, const unsigned int *d_seeds, f64 *d_scale, f64 *d_R, f64 *d_T, s32 *d_inlier, s32 *d_corr_index,
+                 s32 *d_n_inliers, s32 *d_winner, s32 *d_counts, f64 *d_stats, const vslam_sim3_params *params,
+                 const vslam_resect_params *polish) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("sim3_ransac: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_sim3_ransac(ctx, d_A, d_xa, d_B, d_xb, d_n, batch, stride, k, d_seeds, params, polish, d_scale, d_R, d_T, d_inlier,
+                                     d_corr_index, d_n_inliers, d_winner, d_counts, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_sim3_ransac: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
+void sim3_refine(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d_B, const float *d_xb, const s32 *d_n, int batch, int stride,
+                 const s32 *d_mask, const cv::Mat &K, f64 *d_scale, f64 *d_R, f64 *d_T, f64 *d_stats, const vslam_resect_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("sim3_refine: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_sim3_refine(ctx, d_A, d_xa, d_B, d_xb, d_n, batch, stride, d_mask, k, params, d_scale, d_R, d_T, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_sim3_refine: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
 void fuse_points(vslam_ctx *ctx, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const s32 *d_obs_kp,
                  int obs_stride, int cam_stride, int kp_stride, const s32 *d_mask, int batch, s32 *d_fuse_to, s32 *d_out_offsets,
                  s32 *d_out_cam, s32 *d_out_kp, s32 *d_out_src, s32 *d_stats) {
