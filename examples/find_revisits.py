@@ -15,7 +15,13 @@ the ratio of the two baselines, which nothing else in this file knows.  No polis
 the candidate, where the polish cannot see the scale.  Expect "not found" often: two-view points over a short
 baseline are rough, and inlier_px (2 px, both ways) is untuned.
 
-    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256] [--sim3]
+With --close (implies --sim3) the found similarities whose two frames lie in ONE track become loops of that track: the tracks are run
+through Context.track_sequences into a PointMap with a world attached, each model is brought into the world's unit with the world's
+per-pair scales (A and B above are in the units of their own pairs' baselines), and World.close_loops (include/vslam_graph.h) spreads
+every loop's error over the frames between its ends.  The statistics per track are printed: usable edges, mean cost before and
+after, accepted steps.  No policy decides which loops deserve it: every found one is taken.
+
+    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256] [--sim3] [--close]
 """
 import argparse
 import os
@@ -28,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vslam_amd import capi, synth  # noqa: E402
 
 
-def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev):
+def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev, models):
     """{query: text}: for every query with a candidate, three pairs through vslam_frontend_pairs_pose -- (candidate, its neighbour),
     (query, its neighbour), (candidate, query) -- then one batch of Context.sim3_ransac over what the three have in common"""
     width, height, max_corners, hyp = sizes
@@ -74,6 +80,7 @@ def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev):
     ctx.synchronize()
     win, cnt, s, R, T = (r[k].cpu().numpy() for k in ("winner", "n_inliers", "scale", "R", "T"))
     out = {}
+    models.extend((cands[i], q, float(s[i]), R[i].copy(), T[i].copy()) for i, q in enumerate(asked) if win[i] >= 0)
     for i, q in enumerate(asked):
         if win[i] < 0:
             out[q] = f"sim3: not found among {n[i]} 3-D pairs"
@@ -83,6 +90,38 @@ def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev):
     return out
 
 
+def close_loops(ctx, a, bgr, models, sizes, rot, dev):
+    """the found same-track models as loops of a world built from the same frames; prints World.close_loops' statistics"""
+    width, height, max_corners, hyp = sizes
+    cos_a, sin_a, pat = rot
+    K = np.array([[525, 0, width // 2], [0, 525, height // 2], [0, 0, 1]], np.float32)
+    same = [m for m in models if m[0] // a.frames == m[1] // a.frames]
+    print(f"loops: {len(same)} of {len(models)} found similarities join two frames of one track")
+    if not same:
+        return
+    seeds = torch.arange(a.tracks * (a.frames - 1), dtype=torch.int32, device=dev).reshape(a.tracks, a.frames - 1).contiguous()
+    pmap = capi.PointMap(ctx, a.tracks, a.frames, max_corners, map_capacity=a.frames * max_corners, obs_capacity=4 * a.frames * max_corners)
+    world = pmap.attach_world()
+    ctx.track_sequences(pmap, bgr.reshape(a.tracks, a.frames, height, width, 3), max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
+    ctx.synchronize()
+    scale = world.view()["scale"]
+    unit = lambda f: float(scale[f // a.frames, min(f % a.frames + 1, a.frames - 1)])   # the world's scale of the pair f was triangulated in
+    rows, s, R, T = [], [], [], []
+    for c, q, ms, mR, mT in same:   # camera a = the candidate, camera b = the query, both in the world's unit
+        rows.append((c // a.frames, c % a.frames, q % a.frames))
+        s.append(ms * unit(q) / unit(c))
+        R.append(mR)
+        T.append(mT * unit(q))
+    t = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v, dt)).to(dev)
+    stats = world.close_loops(pmap, t(rows, np.int32), t(s, np.float64), t(R, np.float64), t(T, np.float64))
+    ctx.synchronize()
+    for k, st in enumerate(stats.cpu().numpy()):
+        moved = "left alone" if np.isnan(st[3]) else f"cost per edge {st[1]:.3e} -> {st[2]:.3e} in {int(st[3])} steps"
+        print(f"track {k}: {int(st[0])} usable edges, {moved}")
+    world.close()
+    pmap.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tracks", type=int, default=3)
@@ -90,7 +129,9 @@ def main():
     ap.add_argument("--gap", type=int, default=2)
     ap.add_argument("--words", type=int, default=256)
     ap.add_argument("--sim3", action="store_true", help="print the similarity between the best candidate's map and the query's")
+    ap.add_argument("--close", action="store_true", help="close the same-track loops among the found similarities (implies --sim3)")
     a = ap.parse_args()
+    a.sim3 = a.sim3 or a.close
     width, height, max_corners, hyp, top_k = 320, 240, 1000, 256, 3
     dev = torch.device("cuda", 0)
     ctx = capi.Context(0)
@@ -128,7 +169,8 @@ def main():
         ctx.synchronize()
         inliers = dict(zip(asked, out["best"][:, 3].cpu().numpy().tolist()))
 
-    sim3 = similarities(ctx, a, bgr, asked, best_id, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev) if a.sim3 and asked else {}
+    models = []
+    sim3 = similarities(ctx, a, bgr, asked, best_id, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev, models) if a.sim3 and asked else {}
 
     for q in range(N):
         cand = ", ".join(f"({tag[e][0]}, {tag[e][1]}) {s / d:.3f}" for e, s, d in zip(best_id[q], score[q], den[q]) if e >= 0)
@@ -138,6 +180,8 @@ def main():
         if q in sim3:
             line += "; " + sim3[q]
         print(line)
+    if a.close:
+        close_loops(ctx, a, bgr, models, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev)
     idx.close()
     ctx.close()
 

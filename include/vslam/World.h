@@ -13,6 +13,7 @@
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
 #include "../vslam_sim3.h"
+#include "../vslam_graph.h"
 #include "../vslam_fuse.h"
 #include "../vslam_tracks.h"
 
@@ -125,6 +126,17 @@ public:
     void apply_sim3(vslam_map *map, const int32_t *h_track, const double *d_s, const double *d_R, const double *d_t, const int32_t *d_apply,
                     int items) {
         check(vslam_world_apply_sim3(ctx_, world_, map, h_track, d_s, d_R, d_t, d_apply, items), "vslam_world_apply_sim3");
+    }
+    // The loops inside each track closed and their error spread over the frames in between (vslam_world_close_loops,
+    // include/vslam_graph.h: every array is that call's): d_track, d_frame_a, d_frame_b, d_use [loops] and the camera a -> camera b
+    // model d_scale / d_R / d_T of each on the device; seq_weight / loop_weight: three host numbers or nullptr (1 1 1); params:
+    // nullptr for the defaults; d_stats [tracks][4] or nullptr.
+    void close_loops(vslam_map *map, const int32_t *d_track, const int32_t *d_frame_a, const int32_t *d_frame_b, const int32_t *d_use,
+                     const double *d_scale, const double *d_R, const double *d_T, int loops, const double *seq_weight = nullptr,
+                     const double *loop_weight = nullptr, const vslam_graph_params *params = nullptr, double *d_stats = nullptr) {
+        check(vslam_world_close_loops(ctx_, world_, map, d_track, d_frame_a, d_frame_b, d_use, d_scale, d_R, d_T, loops, seq_weight, loop_weight,
+                                      params, d_stats),
+              "vslam_world_close_loops");
     }
     // The map points of every track that share an observation fused into groups (vslam_world_fuse, include/vslam_fuse.h): the
     // world's d_fuse_to written, the rows of the newly absorbed points in d_world_points set to NaN.  The world must be the one

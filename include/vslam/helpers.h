@@ -11,6 +11,7 @@
 #include "../vslam_search.h"
 #include "../vslam_pnp.h"
 #include "../vslam_sim3.h"
+#include "../vslam_graph.h"
 #include "../vslam_fuse.h"
 #include "../vslam_tracks.h"
 #include "../vslam_places.h"
@@ -118,6 +119,13 @@ void sim3_ransac(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d
 void sim3_refine(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d_B, const float *d_xb, const s32 *d_n, int batch, int stride,
                  const s32 *d_mask, const cv::Mat &K, f64 *d_scale, f64 *d_R, f64 *d_T, f64 *d_stats = nullptr,
                  const vslam_resect_params *params = nullptr);
+
+// Pose graphs over Sim(3) for a batch of items the caller holds on the device (vslam_graph_optimize, include/vslam_graph.h: the
+// arrays and strides are that call's), d_scale / d_R / d_T in place; params: nullptr for the defaults; d_stats may be nullptr.
+// Stream-ordered on `ctx`; throws std::runtime_error with vslam_last_error.
+void graph_optimize(vslam_ctx *ctx, f64 *d_scale, f64 *d_R, f64 *d_T, const s32 *d_fixed, const s32 *d_n_nodes, int batch, int node_stride,
+                    const s32 *d_edge_ab, const f64 *d_edge_scale, const f64 *d_edge_R, const f64 *d_edge_T, const f64 *d_edge_weight,
+                    const s32 *d_n_edges, int edge_stride, f64 *d_stats = nullptr, const vslam_graph_params *params = nullptr);
 
 // Map points that share an observation grouped, their observation lists merged, for a batch of items the caller holds on the
 // device (vslam_fuse_points, include/vslam_fuse.h: the arrays and strides are that call's).  d_mask, d_out_src and d_stats may be

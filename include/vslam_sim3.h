@@ -128,8 +128,8 @@
  * VSLAM_ERR_INVALID for a null pointer, items not positive or above the world's tracks, a world that is not the one attached to that
  * map, d_s, d_R or d_t off 8 bytes, d_apply off 4.
  *
- * Left open: spreading a loop's error over the frames between its ends (a pose-graph or Sim(3)-graph optimisation: apply_sim3 moves a
- * whole track rigidly); merging two tracks' point lists into one map; deciding when to accept a loop; an f64 matrix-core count
+ * Spreading a loop's error over the frames between its ends is vslam_graph.h's (vslam_world_close_loops takes a same-track item's
+ * camera-to-camera model as it stands).  Left open: merging two tracks' point lists into one map; deciding when to accept a loop; an f64 matrix-core count
  * (v_mfma_f64_16x16x4 has K = 4 = (x, y, z, 1), but its internal summation order is not this contract's); pushing the verified
  * matches into the map's log.                                                                                                    */
 #ifndef VSLAM_SIM3_H

@@ -115,6 +115,15 @@ class Sim3Params(_Params):
     _fields_ = [("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("inlier_px", C.c_double)]
 
 
+# every symbol include/vslam_graph.h declares (a header of its own; tests/test_graph_lds.py checks it)
+GRAPH_SYMBOLS = ["vslam_graph_params_default", "vslam_graph_optimize", "vslam_world_close_loops"]
+
+
+class GraphParams(_Params):
+    _struct = "vslam_graph_params"
+    _fields_ = [("max_iterations", C.c_int32), ("cg_iterations", C.c_int32), ("cg_tolerance", C.c_double)]
+
+
 # every symbol include/vslam_fuse.h declares (a header of its own; tests/test_gpu_fuse.py checks it)
 FUSE_SYMBOLS = ["vslam_cull_params_default", "vslam_fuse_points", "vslam_cull_points", "vslam_world_fuse", "vslam_world_cull",
                 "vslam_world_observations", "vslam_world_fusion_view"]
@@ -704,6 +713,27 @@ class Context:
         self._ready()
         self._check(self.lib.vslam_sim3_refine(self.handle, _ptr(A), _ptr(xa), _ptr(B), _ptr(xb), _ptr(n), C.c_int(Bt), C.c_int(S), _ptr(mask),
                                                Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(scale), _ptr(R), _ptr(T), _ptr(stats)))
+        return scale, R, T, stats
+
+    def graph_optimize(self, scale, R, T, fixed, n_nodes, edge_ab, edge_scale, edge_R, edge_T, edge_weight, n_edges, want_stats=True, **params):
+        """vslam_graph_optimize (include/vslam_graph.h): each item's pose graph over Sim(3) optimised IN PLACE.  Nodes: scale (B, S), R
+        (B, S, 9 or 3, 3), T (B, S, 3) f64, fixed (B, S) i32, n_nodes (B,) i32; edges: edge_ab (B, Es, 2) i32, edge_scale (B, Es), edge_R
+        (B, Es, 9 or 3, 3), edge_T (B, Es, 3), edge_weight (B, Es, 3) f64, n_edges (B,) i32; params: fields of vslam_graph_params over
+        its defaults.  Returns (scale, R, T, stats (B, 4) f64 or None)."""
+        torch = self.torch
+        B, S = scale.shape
+        Es = edge_scale.shape[1]
+        for x, dt, nm in ((scale, torch.float64, "scale"), (R, torch.float64, "R"), (T, torch.float64, "T"), (fixed, torch.int32, "fixed"),
+                          (n_nodes, torch.int32, "n_nodes"), (edge_ab, torch.int32, "edge_ab"), (edge_scale, torch.float64, "edge_scale"),
+                          (edge_R, torch.float64, "edge_R"), (edge_T, torch.float64, "edge_T"), (edge_weight, torch.float64, "edge_weight"),
+                          (n_edges, torch.int32, "n_edges")):
+            self._dev(x, dt, nm)
+        stats = torch.empty((B, 4), dtype=torch.float64, device=scale.device) if want_stats else None
+        prm = GraphParams.make(self.lib, **params)
+        self._ready()
+        self._check(self.lib.vslam_graph_optimize(self.handle, _ptr(scale), _ptr(R), _ptr(T), _ptr(fixed), _ptr(n_nodes), C.c_int(B), C.c_int(S),
+                                                  _ptr(edge_ab), _ptr(edge_scale), _ptr(edge_R), _ptr(edge_T), _ptr(edge_weight), _ptr(n_edges),
+                                                  C.c_int(Es), C.byref(prm), _ptr(stats)))
         return scale, R, T, stats
 
     def match_points(self, points, n_points, obs_offsets, obs_desc, xy, desc, n_kp, kp_taken=None, out=None, want_indices=True,
@@ -1515,6 +1545,30 @@ class World:
         self.ctx._ready()
         self.ctx._check(self.lib.vslam_world_apply_sim3(self.ctx.handle, self.handle, pmap.handle, h.ctypes.data_as(C.c_void_p), _ptr(s), _ptr(R),
                                                         _ptr(t), _ptr(apply), C.c_int(len(h))))
+
+    def close_loops(self, pmap, loops, scale, R, T, use=None, seq_weight=None, loop_weight=None, **params):
+        """vslam_world_close_loops (include/vslam_graph.h): every track's frames, scales, carry and world points moved so that the
+        loops close, the error spread over the frames in between; this world must be the one attached to `pmap`.  loops: (items, 3)
+        i32 rows (track, frame_a, frame_b); scale (items,), R (items, 9), T (items, 3) f64: the camera a -> camera b model of each, as
+        sim3() returns it for a same-track item; use (items,) i32 (None: all ones); seq_weight / loop_weight: three host numbers each
+        (None: 1 1 1); params: fields of vslam_graph_params.  Returns the statistics (tracks, 4) f64 (a cuda tensor)."""
+        import numpy as np
+        torch = self.ctx.torch
+        items = loops.shape[0]
+        if use is None:
+            use = torch.ones((items,), dtype=torch.int32, device=loops.device)
+        for x, dt, nm in ((loops, torch.int32, "loops"), (use, torch.int32, "use"), (scale, torch.float64, "scale"), (R, torch.float64, "R"),
+                          (T, torch.float64, "T")):
+            self.ctx._dev(x, dt, nm)
+        cols = [loops[:, k].contiguous() for k in range(3)]
+        wts = [None if w is None else np.ascontiguousarray(np.asarray(w, np.float64).reshape(3)) for w in (seq_weight, loop_weight)]
+        stats = torch.empty((self.tracks, 4), dtype=torch.float64, device=loops.device)
+        prm = GraphParams.make(self.lib, **params)
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_close_loops(
+            self.ctx.handle, self.handle, pmap.handle, *(_ptr(c) for c in cols), _ptr(use), _ptr(scale), _ptr(R), _ptr(T), C.c_int(items),
+            *(w.ctypes.data_as(C.c_void_p) if w is not None else C.c_void_p(0) for w in wts), C.byref(prm), _ptr(stats)))
+        return stats
 
     def set_resection(self, enable=True, **params):
         """vslam_world_set_resection (include/vslam_resect.h), allowed at frame 0 only: from now on step() takes xy_cur and K

@@ -922,6 +922,14 @@ void sim3_refine(vslam_ctx *ctx, const f64 *d_A, const float *d_xa, const f64 *d
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_sim3_refine: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
 
+void graph_optimize(vslam_ctx *ctx, f64 *d_scale, f64 *d_R, f64 *d_T, const s32 *d_fixed, const s32 *d_n_nodes, int batch, int node_stride,
+                    const s32 *d_edge_ab, const f64 *d_edge_scale, const f64 *d_edge_R, const f64 *d_edge_T, const f64 *d_edge_weight,
+                    const s32 *d_n_edges, int edge_stride, f64 *d_stats, const vslam_graph_params *params) {
+    const int rc = vslam_graph_optimize(ctx, d_scale, d_R, d_T, d_fixed, d_n_nodes, batch, node_stride, d_edge_ab, d_edge_scale, d_edge_R, d_edge_T,
+                                        d_edge_weight, d_n_edges, edge_stride, params, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_graph_optimize: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
 void fuse_points(vslam_ctx *ctx, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam, const s32 *d_obs_kp,
                  int obs_stride, int cam_stride, int kp_stride, const s32 *d_mask, int batch, s32 *d_fuse_to, s32 *d_out_offsets,
                  s32 *d_out_cam, s32 *d_out_kp, s32 *d_out_src, s32 *d_stats) {
