@@ -15,13 +15,15 @@ the ratio of the two baselines, which nothing else in this file knows.  No polis
 the candidate, where the polish cannot see the scale.  Expect "not found" often: two-view points over a short
 baseline are rough, and inlier_px (2 px, both ways) is untuned.
 
+With --close --project the geometric round (World.fuse_project, include/vslam_fuse_project.h) then runs over the two end frames of every
+closed loop: the world points are searched by projection in those frames, and map points that never shared a keypoint become one track.
 With --close (implies --sim3) the found similarities whose two frames lie in ONE track become loops of that track: the tracks are run
 through Context.track_sequences into a PointMap with a world attached, each model is brought into the world's unit with the world's
 per-pair scales (A and B above are in the units of their own pairs' baselines), and World.close_loops (include/vslam_graph.h) spreads
 every loop's error over the frames between its ends.  The statistics per track are printed: usable edges, mean cost before and
 after, accepted steps.  No policy decides which loops deserve it: every found one is taken.
 
-    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256] [--sim3] [--close]
+    python examples/find_revisits.py [--tracks 3] [--frames 8] [--gap 2] [--words 256] [--sim3] [--close [--project]]
 """
 import argparse
 import os
@@ -90,7 +92,7 @@ def similarities(ctx, a, bgr, asked, best_id, sizes, rot, dev, models):
     return out
 
 
-def close_loops(ctx, a, bgr, models, sizes, rot, dev):
+def close_loops(ctx, a, bgr, models, sizes, rot, dev, project=False):
     """the found same-track models as loops of a world built from the same frames; prints World.close_loops' statistics"""
     width, height, max_corners, hyp = sizes
     cos_a, sin_a, pat = rot
@@ -102,7 +104,7 @@ def close_loops(ctx, a, bgr, models, sizes, rot, dev):
     seeds = torch.arange(a.tracks * (a.frames - 1), dtype=torch.int32, device=dev).reshape(a.tracks, a.frames - 1).contiguous()
     pmap = capi.PointMap(ctx, a.tracks, a.frames, max_corners, map_capacity=a.frames * max_corners, obs_capacity=4 * a.frames * max_corners)
     world = pmap.attach_world()
-    ctx.track_sequences(pmap, bgr.reshape(a.tracks, a.frames, height, width, 3), max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
+    kp = ctx.track_sequences(pmap, bgr.reshape(a.tracks, a.frames, height, width, 3), max_corners, cos_a, sin_a, None, seeds, hyp, 10.0, K)
     ctx.synchronize()
     scale = world.view()["scale"]
     unit = lambda f: float(scale[f // a.frames, min(f % a.frames + 1, a.frames - 1)])   # the world's scale of the pair f was triangulated in
@@ -118,6 +120,12 @@ def close_loops(ctx, a, bgr, models, sizes, rot, dev):
     for k, st in enumerate(stats.cpu().numpy()):
         moved = "left alone" if np.isnan(st[3]) else f"cost per edge {st[1]:.3e} -> {st[2]:.3e} in {int(st[3])} steps"
         print(f"track {k}: {int(st[0])} usable edges, {moved}")
+    if project:   # the geometric round over the two ends of every closed loop (include/vslam_fuse_project.h)
+        world.fuse(pmap)
+        for trk, fa, fb in sorted(set(rows)):
+            for f in sorted({fa, fb}):
+                ps = world.fuse_project(pmap, kp["xy"], kp["desc"], kp["n"], K, width, height, frames=(f, f + 1)).cpu().numpy()
+                print(f"loop of track {trk}, frame {f}: tried {ps[trk, 0]}, found {ps[trk, 3]}, links {ps[trk, 4]}, extras held {ps[trk, 7]}")
     world.close()
     pmap.close()
 
@@ -130,6 +138,7 @@ def main():
     ap.add_argument("--words", type=int, default=256)
     ap.add_argument("--sim3", action="store_true", help="print the similarity between the best candidate's map and the query's")
     ap.add_argument("--close", action="store_true", help="close the same-track loops among the found similarities (implies --sim3)")
+    ap.add_argument("--project", action="store_true", help="with --close: fuse the map points of each closed loop's two ends by projection")
     a = ap.parse_args()
     a.sim3 = a.sim3 or a.close
     width, height, max_corners, hyp, top_k = 320, 240, 1000, 256, 3
@@ -181,7 +190,7 @@ def main():
             line += "; " + sim3[q]
         print(line)
     if a.close:
-        close_loops(ctx, a, bgr, models, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev)
+        close_loops(ctx, a, bgr, models, (width, height, max_corners, hyp), (cos_a, sin_a, pat), dev, project=a.project)
     idx.close()
     ctx.close()
 

@@ -4,7 +4,7 @@ matched once on the device, then the map is advanced one frame at a time (vslam_
 map is drawn on the device (vslam_map_render: the points in their colours, one wire frustum per frame so far) and written as a
 binary PPM.  What the reference shows in its Pangolin window (src/display.cpp), headless.
 
-    python examples/render_map.py [--world [--resect] [--fuse [--cull] [--retriangulate]] [--adjust] [--search] [--relocalise]] [output directory]
+    python examples/render_map.py [--world [--resect] [--fuse [--project] [--cull] [--retriangulate]] [--adjust] [--search] [--relocalise]] [output directory]
 
 --world: the map also gets a world frame (vslam_map_attach_world) and every image is twice as wide: on the left what the
 reference's window shows -- every pair's points in the last frame's camera and in the pair's own unit, stacked at the origin --
@@ -15,6 +15,10 @@ chained from the pair's fundamental matrix alone; the accepted steps and partici
 (World.fuse, include/vslam_fuse.h) and, with --cull, the points their observations do not support are culled (World.cull, at its
 untuned defaults); the world is drawn before and after (track*_before_fuse.ppm / track*_after_fuse.ppm) and the counts are printed.
 --adjust, --search and --relocalise then read the merged observation lists.
+--project (with --fuse, behind it and ahead of --cull): the geometric round (World.fuse_project, include/vslam_fuse_project.h, at the
+search's untuned defaults): every world point is searched by projection in the frames that do not see it yet, the found pairs join
+the world's extra log and the fusion runs over the lists with them; the world is drawn before and after
+(track*_before_project.ppm / track*_after_project.ppm) and the counts are printed.
 --retriangulate (with --fuse, behind it and --cull): every world point is triangulated anew from ALL the observations of its merged
 row (World.retriangulate, include/vslam_tracks.h, at its untuned defaults); the world is drawn before and after
 (track*_before_retriangulate.ppm / track*_after_retriangulate.ppm) and the counts per status are printed.
@@ -48,7 +52,7 @@ def write_ppm(path, bgr):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--fuse", "--cull", "--retriangulate", "--adjust", "--search", "--relocalise")]
+    args = [a for a in sys.argv[1:] if a not in ("--world", "--resect", "--fuse", "--project", "--cull", "--retriangulate", "--adjust", "--search", "--relocalise")]
     with_world = "--world" in sys.argv[1:]
     resect = "--resect" in sys.argv[1:]
     adjust = "--adjust" in sys.argv[1:]
@@ -56,11 +60,12 @@ def main():
     relocalise = "--relocalise" in sys.argv[1:]
     fuse = "--fuse" in sys.argv[1:]
     cull = "--cull" in sys.argv[1:]
+    project = "--project" in sys.argv[1:]
     retri = "--retriangulate" in sys.argv[1:]
     if (resect or adjust or search or relocalise or fuse) and not with_world:
         sys.exit("--resect, --fuse, --adjust, --search and --relocalise need --world")
-    if (cull or retri) and not fuse:
-        sys.exit("--cull and --retriangulate need --fuse")
+    if (cull or retri or project) and not fuse:
+        sys.exit("--project, --cull and --retriangulate need --fuse")
     out_dir = args[0] if args else "render_map_out"
     os.makedirs(out_dir, exist_ok=True)
     tracks, frames, width, height, max_corners, hyp = 4, 8, 640, 480, 1000, 512
@@ -119,6 +124,19 @@ def main():
             world.render(pmap, view, W, H, out=(world_images, None))
             before = world_images.cpu().numpy()
             fs = world.fuse(pmap).cpu().numpy()
+            if project:
+                world.render(pmap, view, W, H, out=(world_images, None))
+                fused = world_images.cpu().numpy()
+                ps = world.fuse_project(pmap, out["xy"], out["desc"], out["n"], K, width, height).cpu().numpy()
+                world.render(pmap, view, W, H, out=(world_images, None))
+                ctx.synchronize()
+                projected = world_images.cpu().numpy()
+                for t in range(tracks):
+                    write_ppm(os.path.join(out_dir, f"track{t}_before_project.ppm"), fused[t])
+                    write_ppm(os.path.join(out_dir, f"track{t}_after_project.ppm"), projected[t])
+                live = [int((world.view()["fuse_to"][t, :sizes[t]] == np.arange(sizes[t])).sum()) for t in range(tracks)]
+                print("geometric round per track: pairs tried", ps[:, 0].tolist(), "found", ps[:, 3].tolist(), "of them links", ps[:, 4].tolist(),
+                      "extras held", ps[:, 7].tolist(), "live points afterwards", live)
             cs = world.cull(pmap, out["xy"], K).cpu().numpy() if cull else None
             world.render(pmap, view, W, H, out=(world_images, None))
             ctx.synchronize()

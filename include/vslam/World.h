@@ -15,6 +15,7 @@
 #include "../vslam_sim3.h"
 #include "../vslam_graph.h"
 #include "../vslam_fuse.h"
+#include "../vslam_fuse_project.h"
 #include "../vslam_tracks.h"
 
 namespace vslam {
@@ -147,6 +148,15 @@ public:
     void cull(vslam_map *map, const float *d_xy, int xy_frames, const float *h_K, const vslam_cull_params *params = nullptr,
               int32_t *d_stats = nullptr) {
         check(vslam_world_cull(ctx_, world_, map, d_xy, xy_frames, h_K, params, d_stats), "vslam_world_cull");
+    }
+    // Geometric fusing (vslam_world_fuse_project, include/vslam_fuse_project.h): every world point searched by projection in the
+    // recorded frames frame_lo <= f < frame_hi that do not see it yet, the found pairs appended to the world's extra log, then what
+    // fuse() does over the lists with the extras in them.  d_xy / d_desc / d_n_kp: the keypoints of every frame,
+    // [tracks][xy_frames][kp_stride]; search: nullptr for the defaults; d_stats [tracks][8] int32 or nullptr.
+    void fuse_project(vslam_map *map, const float *d_xy, const uint8_t *d_desc, const int32_t *d_n_kp, int xy_frames, const float *h_K, int width,
+                      int height, int frame_lo, int frame_hi, const vslam_search_params *search = nullptr, int32_t *d_stats = nullptr) {
+        check(vslam_world_fuse_project(ctx_, world_, map, d_xy, d_desc, d_n_kp, xy_frames, h_K, width, height, frame_lo, frame_hi, search, d_stats),
+              "vslam_world_fuse_project");
     }
     // Every world point triangulated anew from all the observations of its row of the world's CSR, in place; only the rows that come
     // out with status 0 are written (vslam_world_retriangulate, include/vslam_tracks.h).  d_xy as adjust() takes it; params: nullptr

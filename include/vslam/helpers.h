@@ -13,6 +13,7 @@
 #include "../vslam_sim3.h"
 #include "../vslam_graph.h"
 #include "../vslam_fuse.h"
+#include "../vslam_fuse_project.h"
 #include "../vslam_tracks.h"
 #include "../vslam_places.h"
 #include "Frame.h"
@@ -141,6 +142,16 @@ void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, i
                  const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride, const float *d_xy,
                  int kp_stride, const cv::Mat &K, int batch, s32 *d_keep, s32 *d_stats, s32 *d_counts = nullptr,
                  const vslam_cull_params *params = nullptr);
+
+// Geometric fusing: every point of each item searched by projection in every camera that does not see it yet, one-to-one per
+// keypoint, with the point that already holds the keypoint (vslam_fuse_project, include/vslam_fuse_project.h: the arrays and strides
+// are that call's).  K: 3 x 3 CV_32F; params: nullptr for the defaults; d_cam_mask and d_stats may be nullptr.  Stream-ordered on
+// `ctx`; throws std::runtime_error with vslam_last_error.
+void fuse_project(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam,
+                  const s32 *d_obs_kp, const u8 *d_obs_desc, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride,
+                  const float *d_xy, const u8 *d_desc, const s32 *d_n_kp, int kp_stride, const s32 *d_cam_mask, const cv::Mat &K, int width,
+                  int height, int batch, s32 *d_found_point, s32 *d_found_cam, s32 *d_found_kp, s32 *d_found_dist, s32 *d_found_holder,
+                  int found_stride, s32 *d_n_found, s32 *d_stats = nullptr, const vslam_search_params *params = nullptr);
 
 // Each point of each item triangulated from all its observations (vslam_triangulate_tracks, include/vslam_tracks.h: the arrays and
 // strides are that call's; d_out_points may be d_points).  K: 3 x 3 CV_32F; params: nullptr for the defaults; d_counts and d_info may

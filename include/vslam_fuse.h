@@ -104,7 +104,8 @@
  * Workspace from the arena: vslam_fuse_points' own plus tracks x (2 map_capacity + 1 + 5 obs_capacity) x 4 bytes, and tracks x
  * obs_capacity x 32 where descriptors are gathered.
  *
- * Left open: geometric fusing through a search by projection (points that never shared a keypoint); running behind every step;
+ * Geometric fusing through a search by projection (points that never shared a keypoint) is vslam_fuse_project.h's, whose extras
+ * enter the world's CSR above as further entries of the map's log.  Left open: running behind every step;
  * tuning on footage.  The survivor keeps its own position here: vslam_world_retriangulate (vslam_tracks.h) gives every track the
  * position all its observations support, with a parallax test as one of its refusals.                                          */
 #ifndef VSLAM_FUSE_H

@@ -129,7 +129,7 @@
  * map, d_s, d_R or d_t off 8 bytes, d_apply off 4.
  *
  * Spreading a loop's error over the frames between its ends is vslam_graph.h's (vslam_world_close_loops takes a same-track item's
- * camera-to-camera model as it stands).  Left open: merging two tracks' point lists into one map; deciding when to accept a loop; an f64 matrix-core count
+ * camera-to-camera model as it stands).  Left open: merging two tracks' point lists into one map (the two ends of a loop INSIDE a track: vslam_fuse_project.h); deciding when to accept a loop; an f64 matrix-core count
  * (v_mfma_f64_16x16x4 has K = 4 = (x, y, z, 1), but its internal summation order is not this contract's); pushing the verified
  * matches into the map's log.                                                                                                    */
 #ifndef VSLAM_SIM3_H

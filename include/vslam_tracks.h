@@ -95,7 +95,7 @@
  * Workspace from the context's arena, allocated on the first call of a size and never afterwards: what forms the world's CSR
  * (vslam_fuse.h) plus tracks x (map_capacity + 6 + 2 obs_capacity) x 4 + tracks x max_frames x 96 bytes.
  *
- * Left open: running behind a step; geometric fusing through a search by projection; tuning on footage; culling by parallax as a
+ * Left open: running behind a step (geometric fusing through a search by projection is vslam_fuse_project.h's); tuning on footage; culling by parallax as a
  * policy (here it is only a status: a refused point keeps its row).                                                            */
 #ifndef VSLAM_TRACKS_H
 #define VSLAM_TRACKS_H

@@ -13,8 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvslam_amd.so")
 SOURCES = ["capi.hip", "match.hip", "ransac_sets.hip", "ransac_solve.hip", "ransac_count.hip", "ransac_prune.hip", "ransac_select.hip", "refit.hip", "refine.hip",
            "kdtree.hip", "gray.hip", "response.hip", "select.hip", "blur.hip",
-           "brief.hip", "orb_grid.hip", "pose.hip", "assoc.hip", "map.hip", "world.hip", "resect.hip", "adjust.hip", "search.hip", "pnp.hip", "sim3.hip", "graph.hip", "fuse.hip", "tracks.hip", "places.hip", "render.hip", "multi.hip", "pipeline.hip"]
-HEADERS = ["ctx.h", "introselect.h", "image_common.h", "ransac_svd.h", "ransac_residual.h", "ransac_prune_cert.h", "ransac_prune_tile.h", "block_reduce.h", "block_scan.h", "lm_math.h", "refine_math.h", "resect_math.h", "adjust_math.h", "search_math.h", "pnp_math.h", "sim3_math.h", "graph_math.h", "fuse_math.h", "tracks_math.h", "places_math.h", "world_select.h", "world_match.h",
+           "brief.hip", "orb_grid.hip", "pose.hip", "assoc.hip", "map.hip", "world.hip", "resect.hip", "adjust.hip", "search.hip", "pnp.hip", "sim3.hip", "graph.hip", "fuse.hip", "fuse_project.hip", "tracks.hip", "places.hip", "render.hip", "multi.hip", "pipeline.hip"]
+HEADERS = ["ctx.h", "introselect.h", "image_common.h", "ransac_svd.h", "ransac_residual.h", "ransac_prune_cert.h", "ransac_prune_tile.h", "block_reduce.h", "block_scan.h", "lm_math.h", "refine_math.h", "resect_math.h", "adjust_math.h", "search_math.h", "pnp_math.h", "sim3_math.h", "graph_math.h", "fuse_math.h", "fuse_project_math.h", "tracks_math.h", "places_math.h", "world_select.h", "world_match.h",
            os.path.join("..", "..", "include", "vslam_amd.h"),
            os.path.join("..", "..", "include", "vslam_resect.h"),
            os.path.join("..", "..", "include", "vslam_adjust.h"),
@@ -23,6 +23,7 @@ HEADERS = ["ctx.h", "introselect.h", "image_common.h", "ransac_svd.h", "ransac_r
            os.path.join("..", "..", "include", "vslam_sim3.h"),
            os.path.join("..", "..", "include", "vslam_graph.h"),
            os.path.join("..", "..", "include", "vslam_fuse.h"),
+           os.path.join("..", "..", "include", "vslam_fuse_project.h"),
            os.path.join("..", "..", "include", "vslam_tracks.h"),
            os.path.join("..", "..", "include", "vslam_places.h"),
            os.path.join("..", "..", "include", "vslam_brief_pattern_31.h")]

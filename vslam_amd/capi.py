@@ -135,6 +135,10 @@ class CullParams(_Params):
                 ("good10", C.c_int32)]
 
 
+# every symbol include/vslam_fuse_project.h declares (a header of its own; tests/test_fuse_project_lds.py checks it)
+FUSE_PROJECT_SYMBOLS = ["vslam_fuse_project", "vslam_world_fuse_project", "vslam_world_fuse_project_view"]
+
+
 # every symbol include/vslam_tracks.h declares (a header of its own; tests/test_gpu_tracks.py checks it)
 TRACK_SYMBOLS = ["vslam_track_params_default", "vslam_triangulate_tracks", "vslam_world_retriangulate"]
 
@@ -793,6 +797,42 @@ class Context:
             _ptr(o.get("counts")), _ptr(o["stats"])))
         return o
 
+    def fuse_project(self, points, n_points, obs_offsets, obs_cam, obs_kp, obs_desc, R, T, n_cams, xy, desc, n_kp, K, width, height,
+                     cam_mask=None, found_stride=None, out=None, want_stats=True, **params):
+        """vslam_fuse_project (include/vslam_fuse_project.h): each item's points (B, S, 4) f32 with their observations in CSR
+        (obs_offsets (B, S + 1), obs_cam / obs_kp (B, O) i32, obs_desc (B, O, 32) u8) searched by projection in every camera that does
+        not see them yet: R (B, Cs, 9) / T (B, Cs, 3) f64, n_cams (B,) i32, the cameras' keypoints xy (B, Cs, Kp, 2) f32, desc (B, Cs,
+        Kp, 32) u8, n_kp (B, Cs) i32, cam_mask (B, Cs) i32 or None, K (the 3 x 3 camera matrix, host); params: fields of
+        vslam_search_params over its defaults.  found_stride: slots per item (None: obs_offsets' O).  out: a dict of output tensors to
+        write into (missing ones are made, zero-filled).  Returns the dict: found_point, found_cam, found_kp, found_dist,
+        found_holder (B, found_stride); n_found (B,); stats (B, 6) (want_stats), all i32."""
+        import numpy as np
+        torch = self.torch
+        B, S, O, Cs, Kp = points.shape[0], points.shape[1], obs_cam.shape[1], R.shape[1], xy.shape[2]
+        for x, dt, nm in ((points, torch.float32, "points"), (n_points, torch.int32, "n_points"), (obs_offsets, torch.int32, "obs_offsets"),
+                          (obs_cam, torch.int32, "obs_cam"), (obs_kp, torch.int32, "obs_kp"), (obs_desc, torch.uint8, "obs_desc"),
+                          (R, torch.float64, "R"), (T, torch.float64, "T"), (n_cams, torch.int32, "n_cams"), (xy, torch.float32, "xy"),
+                          (desc, torch.uint8, "desc"), (n_kp, torch.int32, "n_kp"), (cam_mask, torch.int32, "cam_mask")):
+            self._dev(x, dt, nm)
+        if tuple(obs_offsets.shape) != (B, S + 1):
+            raise ValueError(f"obs_offsets has shape {tuple(obs_offsets.shape)}, not {(B, S + 1)}")
+        Fs = O if found_stride is None else int(found_stride)
+        shapes = {k: ((B, Fs), torch.int32) for k in ("found_point", "found_cam", "found_kp", "found_dist", "found_holder")}
+        shapes.update(n_found=((B,), torch.int32))
+        if want_stats:
+            shapes.update(stats=((B, 6), torch.int32))
+        o = self._outputs(out, shapes, points.device)
+        prm = SearchParams.make(self.lib, **params)
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        self._ready()
+        self._check(self.lib.vslam_fuse_project(
+            self.handle, _ptr(points), _ptr(n_points), C.c_int(S), _ptr(obs_offsets), _ptr(obs_cam), _ptr(obs_kp), _ptr(obs_desc), C.c_int(O),
+            _ptr(R), _ptr(T), _ptr(n_cams), C.c_int(Cs), _ptr(xy), _ptr(desc), _ptr(n_kp), C.c_int(Kp), _ptr(cam_mask),
+            Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height), C.c_int(B), C.byref(prm), _ptr(o["found_point"]),
+            _ptr(o["found_cam"]), _ptr(o["found_kp"]), _ptr(o["found_dist"]), _ptr(o["found_holder"]), C.c_int(Fs), _ptr(o["n_found"]),
+            _ptr(o.get("stats"))))
+        return o
+
     def triangulate_tracks(self, points, n_points, obs_offsets, obs_cam, obs_kp, R, T, n_cams, xy, K, out=None, want_counts=True,
                            want_info=True, **params):
         """vslam_triangulate_tracks (include/vslam_tracks.h): each of an item's points (B, S, 4) f32 triangulated from all its
@@ -1404,6 +1444,32 @@ class World:
                                                   Kh.ctypes.data_as(C.c_void_p), C.byref(prm), _ptr(stats)))
         return stats
 
+    def fuse_project(self, pmap, xy, desc, n_kp, K, width, height, frames=None, search=None):
+        """vslam_world_fuse_project (include/vslam_fuse_project.h): every world point searched by projection in every recorded frame
+        that does not see it yet, the found pairs appended to the world's extra log, and the fusion run over the map's lists with the
+        extras in them -- so that map points that never shared a keypoint become one track.  xy / desc / n_kp: the keypoints of every
+        frame, (tracks, xy_frames, kp_stride, 2) f32, (.., kp_stride, 32) u8 and (tracks, xy_frames) i32; frames: (lo, hi), the
+        cameras lo <= f < hi take part (None: every recorded frame); search: a dict of vslam_search_params fields over its defaults.
+        Returns the statistics (tracks, 8) i32 (a cuda tensor): pairs tried, visible, proposing, found, found with a holder, written,
+        extras appended by this call, extras held afterwards."""
+        import numpy as np
+        torch = self.ctx.torch
+        self.ctx._dev(xy, torch.float32, "xy")
+        self.ctx._dev(desc, torch.uint8, "desc")
+        self.ctx._dev(n_kp, torch.int32, "n_kp")
+        xy_frames = xy.numel() // (self.tracks * self.kp_stride * 2)
+        if desc.numel() != self.tracks * xy_frames * self.kp_stride * 32 or n_kp.numel() != self.tracks * xy_frames:
+            raise ValueError(f"desc / n_kp do not hold {self.tracks} x {xy_frames} frames of {self.kp_stride} keypoints")
+        lo, hi = (0, int(self.arrays().frames)) if frames is None else frames
+        Kh = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        stats = torch.zeros((self.tracks, 8), dtype=torch.int32, device=xy.device)
+        prm = SearchParams.make(self.lib, **(search or {}))
+        self.ctx._ready()
+        self.ctx._check(self.lib.vslam_world_fuse_project(self.ctx.handle, self.handle, pmap.handle, _ptr(xy), _ptr(desc), _ptr(n_kp),
+                                                          C.c_int(xy_frames), Kh.ctypes.data_as(C.c_void_p), C.c_int(width), C.c_int(height),
+                                                          C.c_int(lo), C.c_int(hi), C.byref(prm), _ptr(stats)))
+        return stats
+
     def retriangulate(self, pmap, xy, K, want_status=True, **params):
         """vslam_world_retriangulate (include/vslam_tracks.h): every world point triangulated anew from all the observations of its
         row of the world's CSR, in place; xy: the keypoints of every frame as adjust() takes them; params: fields of
@@ -1633,6 +1699,14 @@ class World:
         self.ctx._check(self.lib.vslam_world_fusion_view(self.handle, C.byref(fuse_to), C.c_void_p(0)))
         if fuse_to.value:   # only while a fusion exists; PointMap.view() shows it as world_fuse_to
             v["fuse_to"] = get(fuse_to.value, (T, int(a.map_capacity)), np.int32)
+        log = [C.c_void_p() for _ in range(5)]
+        cap = C.c_int32()
+        self.ctx._check(self.lib.vslam_world_fuse_project_view(self.handle, *(C.byref(p) for p in log), C.byref(cap)))
+        if log[4].value:   # only while extras exist (include/vslam_fuse_project.h); PointMap.view() shows it as world_extra
+            O = int(cap.value)
+            v["extra"] = dict(point=get(log[0].value, (T, O), np.int32), frame=get(log[1].value, (T, O), np.int32),
+                              kp=get(log[2].value, (T, O), np.int32), desc=get(log[3].value, (T, O, 32), np.uint8),
+                              n=get(log[4].value, (T,), np.int32))
         return v
 
     def render(self, pmap, view, width, height, tracks=None, depth=False, row_stride=None, out=None):

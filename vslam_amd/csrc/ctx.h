@@ -373,6 +373,11 @@ struct vslam_world {
     // 0 = "no fusion", d_fuse_to (if made) the identity
     int32_t *fuse_to = nullptr;          // [tracks][map_capacity]
     int fusion = 0;
+    // include/vslam_fuse_project.h: the extra log, made by the first vslam_world_fuse_project; fusion bit 2: extras exist
+    int32_t *extra_point = nullptr, *extra_frame = nullptr, *extra_kp = nullptr;   // [tracks][extra_capacity]
+    uint8_t *extra_desc = nullptr;       // [tracks][extra_capacity][32]
+    int32_t *n_extra = nullptr;          // [tracks]
+    int extra_capacity = 0;              // the map's obs_capacity when the log was made
     std::vector<void *> owned;
 };
 int vs_world_bind(vslam_ctx *ctx, vslam_world *w, int map_capacity);
@@ -420,6 +425,16 @@ int vs_world_csr(vslam_ctx *ctx, vslam_world *world, vslam_map *map, int32_t *of
 // camera f = recorded frame f of every track, from d_Twc as include/vslam_adjust.h forms "camera c" (fuse.hip's world_cameras_kernel):
 // R [tracks][max_frames][9], T [tracks][max_frames][3], n_cams [tracks] = frames
 int vs_world_cameras(vslam_ctx *ctx, vslam_world *world, int max_frames, int frames, double *R, double *T, int32_t *n_cams);
-int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world);   // "no fusion": d_fuse_to (if made) the identity
+int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world);   // "no fusion": d_fuse_to (if made) the identity, the extra log empty
+// d_fuse_to made if the world has none yet (a vs_world_fusion_reset then: so ahead of anything that vslam_world_fuse is to keep)
+int vs_world_fusion_make(vslam_ctx *ctx, vslam_world *world);
+// fuse_project.hip, for a world whose extras exist (include/vslam_fuse_project.h, "The world's CSR once extras exist").  The map's
+// log (log_off [tracks][P + 1], log_frame / log_kp [tracks][O], sizes [tracks]) with every point's admitted extras appended to its
+// row: off [tracks][P + 1], frame / kp / src [tracks][O] (src: the map's row, or O + e for extra e); work [tracks][2 P].
+int vs_world_extras_merge(vslam_ctx *ctx, vslam_world *world, const int32_t *sizes, int P, int O, const int32_t *log_off, const int32_t *log_frame,
+                          const int32_t *log_kp, int32_t *off, int32_t *frame, int32_t *kp, int32_t *src, int32_t *work);
+// the descriptors of a fusion's merged rows over such lists: row o is the map's row or the extra that src[out_src[o]] names
+int vs_world_extras_gather_desc(vslam_ctx *ctx, vslam_world *world, int P, int O, const int32_t *out_off, const int32_t *out_src, const int32_t *src,
+                                const uint8_t *log_desc, uint8_t *desc);
 struct vslam_match_params;   // include/vslam_pnp.h
 bool vs_match_params_ok(const vslam_match_params &p);   // search.hip

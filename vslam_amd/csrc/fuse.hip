@@ -384,12 +384,24 @@ int world_fuse_run(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const vsl
     }
     if ((rc = vslam_map_observations(ctx, map, log_off, log_frame, log_kp))) return rc;
     if (desc && (rc = vslam_map_observation_descriptors(ctx, map, log_off, log_desc))) return rc;
+    const int32_t *in_off = log_off, *in_frame = log_frame, *in_kp = log_kp;
+    int32_t *ext_src = nullptr;
+    if (world->fusion & 4) {   // extras exist (include/vslam_fuse_project.h): the fusion's input is the log with them appended
+        if ((rc = vs_arena_get(ctx, "world_fuse_extras", sizeof(int32_t) * T * ((P + 1) + 3 * O + 2 * P), &ptr))) return rc;
+        int32_t *ext_off = static_cast<int32_t *>(ptr), *ext_frame = ext_off + T * (P + 1), *ext_kp = ext_frame + T * O;
+        ext_src = ext_kp + T * O;
+        if ((rc = vs_world_extras_merge(ctx, world, static_cast<const int32_t *>(m.d_sizes), m.map_capacity, m.obs_capacity, log_off, log_frame, log_kp,
+                                        ext_off, ext_frame, ext_kp, ext_src, ext_src + T * O)))
+            return rc;
+        in_off = ext_off; in_frame = ext_frame; in_kp = ext_kp;
+    }
     FuseArgs a;
-    a.n_points = static_cast<const int32_t *>(m.d_sizes); a.pt_stride = m.map_capacity; a.off = log_off; a.cam = log_frame; a.kp = log_kp;
+    a.n_points = static_cast<const int32_t *>(m.d_sizes); a.pt_stride = m.map_capacity; a.off = in_off; a.cam = in_frame; a.kp = in_kp;
     a.obs_stride = m.obs_capacity; a.cam_stride = m.max_frames; a.kp_stride = m.kp_stride; a.mask = world->fuse_to;
     a.fuse_to = to ? to : tmp_to; a.out_off = off; a.out_cam = frame ? frame : tmp_frame; a.out_kp = kp ? kp : tmp_kp; a.out_src = src;
     a.stats = stats;
     if ((rc = launch_fuse(ctx, a, m.tracks))) return rc;
+    if (desc && ext_src) return vs_world_extras_gather_desc(ctx, world, m.map_capacity, m.obs_capacity, off, src, ext_src, log_desc, desc);
     if (desc) {
         VsProfScope ps(ctx, "fuse_gather_desc_kernel");
         fuse_gather_desc_kernel<<<dim3(vs_div_up(2 * m.obs_capacity, kFT), m.tracks), kFT, 0, ctx->stream>>>(
@@ -402,11 +414,14 @@ int world_fuse_run(vslam_ctx *ctx, vslam_world *world, vslam_map *map, const vsl
 
 int vs_world_fusion_reset(vslam_ctx *ctx, vslam_world *world) {
     world->fusion = 0;
+    if (world->n_extra) VS_HIP(ctx, hipMemsetAsync(world->n_extra, 0, sizeof(int32_t) * (size_t)world->tracks, ctx->stream));
     if (!world->fuse_to) return VSLAM_OK;
     fuse_identity_kernel<<<dim3(vs_div_up(world->map_capacity, kFT), world->tracks), kFT, 0, ctx->stream>>>(world->fuse_to, world->map_capacity);
     VS_HIP(ctx, hipGetLastError());
     return VSLAM_OK;
 }
+
+int vs_world_fusion_make(vslam_ctx *ctx, vslam_world *world) { return world_fusion_make(ctx, world); }
 
 int vs_world_cameras(vslam_ctx *ctx, vslam_world *world, int max_frames, int frames, double *R, double *T, int32_t *n_cams) {
     world_cameras_kernel<<<world->tracks, kFT, 0, ctx->stream>>>(world->Twc, max_frames, frames, R, T, n_cams);

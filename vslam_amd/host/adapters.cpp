@@ -949,6 +949,20 @@ void cull_points(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, i
     if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_cull_points: ") + (ctx ? vslam_last_error(ctx) : "null context"));
 }
 
+void fuse_project(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets, const s32 *d_obs_cam,
+                  const s32 *d_obs_kp, const u8 *d_obs_desc, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams, int cam_stride,
+                  const float *d_xy, const u8 *d_desc, const s32 *d_n_kp, int kp_stride, const s32 *d_cam_mask, const cv::Mat &K, int width,
+                  int height, int batch, s32 *d_found_point, s32 *d_found_cam, s32 *d_found_kp, s32 *d_found_dist, s32 *d_found_holder,
+                  int found_stride, s32 *d_n_found, s32 *d_stats, const vslam_search_params *params) {
+    if (K.rows != 3 || K.cols != 3 || K.type() != CV_32FC1) throw std::invalid_argument("fuse_project: K must be a 3 x 3 CV_32F matrix");
+    float k[9];
+    for (int r = 0; r < 3; r++) std::memcpy(k + 3 * r, K.ptr<float>(r), sizeof(float) * 3);
+    const int rc = vslam_fuse_project(ctx, d_points, d_n_points, pt_stride, d_obs_offsets, d_obs_cam, d_obs_kp, d_obs_desc, obs_stride, d_R, d_T,
+                                      d_n_cams, cam_stride, d_xy, d_desc, d_n_kp, kp_stride, d_cam_mask, k, width, height, batch, params,
+                                      d_found_point, d_found_cam, d_found_kp, d_found_dist, d_found_holder, found_stride, d_n_found, d_stats);
+    if (rc != VSLAM_OK) throw std::runtime_error(std::string("vslam_fuse_project: ") + (ctx ? vslam_last_error(ctx) : "null context"));
+}
+
 void triangulate_tracks(vslam_ctx *ctx, const float *d_points, const s32 *d_n_points, int pt_stride, const s32 *d_obs_offsets,
                         const s32 *d_obs_cam, const s32 *d_obs_kp, int obs_stride, const f64 *d_R, const f64 *d_T, const s32 *d_n_cams,
                         int cam_stride, const float *d_xy, int kp_stride, const cv::Mat &K, int batch, float *d_out_points, s32 *d_status,
