@@ -1,6 +1,8 @@
 """What the tests of vslam_graph_optimize share: the serial program (tests/native/graph_serial.cpp) built once with the sanitizers
 and run over a list of items, the shapes and the hand cases, and each item's reference result computed once per process.  An item is
-ref_graph.pack()'s dict; `prm` holds the vslam_graph_params fields it runs under."""
+ref_graph.pack()'s dict; `prm` holds the vslam_graph_params fields it runs under.  SHAPES and the hand cases are consistent graphs
+under unit weights (the minimum costs 0); LOOP_CASES are the weighted ones whose loops disagree, each under a fixed flow and some
+run to convergence, with the checks both regimes share (hold_flow, hold_converged, same_under_scaled_weights)."""
 import os
 import struct
 import subprocess
@@ -79,6 +81,120 @@ def shape_item(k, node_stride=None, edge_stride=None):
         it["truth"] = truth
         _SHAPES[key] = it
     return _SHAPES[key]
+
+
+# ------------------------------------------------------------------------------------------------ loops that disagree, weights that differ
+# name -> the fixed-flow fields over ref_graph.FLOW.  Every item has per-edge, per-group weights from [0.25, 4] and a minimum with
+# cost > 0.  cg_iterations is small enough that the conjugate gradient is cut far above its floor (test_ref_graph.py asserts
+# rho' / rho_0 >= FLOW_RATIO at every exit): 10 on the short chains, 5 on the pieces of 32; 2 where the edges meet one hub, which
+# block-Jacobi nearly solves.
+LOOP_CASES = [("drift16", dict(max_iterations=3, cg_iterations=10)),     # drifting(16) and a loop 8 -> 1
+              ("drift48", dict(max_iterations=3, cg_iterations=10)),     # drifting(48) and a loop 24 -> 1; ONE zero weight
+              ("hub", dict(max_iterations=3, cg_iterations=2)),          # 8 nodes, 600 edges at free node 1: three fill chunks, multi-edges
+              ("hub257", dict(max_iterations=2, cg_iterations=2)),       # 3 nodes, 257 edges: one edge in the second chunk
+              ("star300", dict(max_iterations=2, cg_iterations=2)),      # hub 299, 600 + 100 edges, leaves without an edge: sums over inactive nodes
+              ("capacity", dict(max_iterations=2, cg_iterations=5)),     # VSLAM_GRAPH_MAX_NODES x VSLAM_GRAPH_MAX_EDGES, every measurement moved
+              ("both_caps", dict(max_iterations=1, cg_iterations=1))]    # drift16: one solve of one iteration
+CONVERGED_CASES = ["drift16", "drift48", "hub"]
+DRIFT_LOOPS = {"drift16": 16, "drift48": 48, "both_caps": 16}
+ZERO_WEIGHT = ("drift48", (24, 1))   # w_t of the edge 24 -> 25: both nodes have other edges
+# Factors that every weight of an item may take without a bit of the result changing.  EVEN powers of two: the preconditioner's
+# Cholesky factor scales by the factor's square root, which is exact for 4 and 2^-4 and is not for 2^-3 (under 2^-3 the serial walk
+# of drift16 ends some last places away, as it must).
+WEIGHT_SCALES = (4.0, 2.0 ** -4)
+_LOOPS = {}
+
+
+def _loop_base(name):
+    if name in DRIFT_LOOPS:
+        N = DRIFT_LOOPS[name]
+        it, truth = rg.weighted_drift(N, 0)
+        if name == ZERO_WEIGHT[0]:
+            it["zw"][ZERO_WEIGHT[1]] = 0.0
+    elif name == "hub":
+        it, truth = rg.star(8, 1, 600, 0, [0, 2, 3, 4, 5, 6, 7])
+        it = rg.weighted(it, 8)
+    elif name == "hub257":
+        it, truth = rg.star(3, 1, 257, 0, [0, 2])
+        it = rg.weighted(it, 3)
+    elif name == "star300":
+        it, truth = rg.star(300, 299, 700, 0, [i for i in range(299) if i % 7 != 3], ring=100)
+        it = rg.weighted(it, 300)
+    elif name == "capacity":
+        it, truth = rg.consistent(rg.MAX_NODES, rg.MAX_EDGES - (rg.MAX_NODES - 1), 0, fixed_every=32)
+        it = rg.weighted(rg.perturbed(it, 0), 4096)
+    else:
+        raise KeyError(name)
+    it["truth"] = truth
+    return it
+
+
+def loop_item(name, regime="flow"):
+    """a LOOP_CASES item under its fixed flow ("flow") or run to convergence ("converged"), made once per process; both regimes
+    share the arrays"""
+    if name not in _LOOPS:
+        _LOOPS[name] = {"base": _loop_base(name)}
+    if regime not in _LOOPS[name]:
+        prm = dict(rg.FLOW, **dict(LOOP_CASES)[name]) if regime == "flow" else dict(rg.CONVERGED)
+        _LOOPS[name][regime] = dict(_LOOPS[name]["base"], prm=prm, name=f"{name} {regime}")
+    return _LOOPS[name][regime]
+
+
+def scaled(it, factor):
+    """the item with every weight multiplied by `factor`"""
+    out = dict(it)
+    out["zw"] = it["zw"] * factor
+    return out
+
+
+def hold_flow(name, got, it, against=None):
+    """a fixed-flow result against the item's reference (and `against`): the integers exact -- usable edges, accepted steps ==
+    max_iterations, the written set --, the nodes and statistics 1 .. 2 within 16 x DELTA_FLOW -> the distance"""
+    ref = reference(it)
+    assert ref["info"]["moved"], name
+    assert got["stats"][0] == ref["stats"][0], (name, got["stats"][0], ref["stats"][0])
+    assert got["stats"][3] == ref["stats"][3] == it["prm"]["max_iterations"], (name, got["stats"][3])
+    w = written(got, it)
+    assert np.array_equal(w, ref["info"]["written"]), (name, np.flatnonzero(w != ref["info"]["written"]))
+    d = 0.0
+    for other in (ref,) + ((against,) if against is not None else ()):
+        d = max(d, rg.distance((got["scale"], got["R"], got["T"]), (other["scale"], other["R"], other["T"]), ref["info"]["written"]))
+        d = max(d, float(np.abs(got["stats"][1:3] / other["stats"][1:3] - 1.0).max()))
+    print(f"{name}: {d:.3e} (bound {16 * rg.DELTA_FLOW:.3e}), cost {got['stats'][1]:.6e} -> {got['stats'][2]:.6e}")
+    assert d <= 16 * rg.DELTA_FLOW, (name, d)
+    return d
+
+
+def hold_converged(name, got, it, against=None):
+    """a converged result against the item's reference (and `against`): usable edges and the written set exact, the final cost
+    within 16 x CONVERGED_COST relative, the nodes within 16 x CONVERGED_NODES -> (the distance, the cost's relative difference)"""
+    ref = reference(it)
+    assert ref["info"]["moved"], name
+    assert got["stats"][0] == ref["stats"][0], name
+    w = written(got, it)
+    assert np.array_equal(w, ref["info"]["written"]), (name, np.flatnonzero(w != ref["info"]["written"]))
+    assert got["stats"][3] >= 1 and got["stats"][2] < got["stats"][1], name
+    d = c = 0.0
+    for other in (ref,) + ((against,) if against is not None else ()):
+        d = max(d, rg.distance((got["scale"], got["R"], got["T"]), (other["scale"], other["R"], other["T"]), ref["info"]["written"]))
+        c = max(c, abs(float(got["stats"][2] / other["stats"][2]) - 1.0), abs(float(got["stats"][1] / other["stats"][1]) - 1.0))
+    print(f"{name}: nodes {d:.3e} (bound {16 * rg.CONVERGED_NODES:.3e}), cost {c:.3e} relative (bound {16 * rg.CONVERGED_COST:.3e}), "
+          f"{int(got['stats'][3])} steps")
+    assert d <= 16 * rg.CONVERGED_NODES and c <= 16 * rg.CONVERGED_COST, (name, d, c)
+    return d, c
+
+
+def same_under_scaled_weights(name, one, got, factor):
+    """`got` ran the item of `one` with every weight times `factor`, a power of two"""
+    for k in ("scale", "R", "T"):
+        assert same_bits(one[k], got[k]), (name, factor, k)
+    assert got["stats"][0] == one["stats"][0] and got["stats"][3] == one["stats"][3], (name, factor)
+    assert same_bits(got["stats"][1:3], one["stats"][1:3] * factor), (name, factor, got["stats"].tolist(), one["stats"].tolist())
+
+
+def drift_ratio(got, it):
+    """(centre error after) / (centre error before) of a drift item"""
+    return rg.centre_error(got["T"], it["truth"]) / rg.centre_error(it["T"], it["truth"])
 
 
 def same_bits(a, b):

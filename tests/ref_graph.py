@@ -9,6 +9,14 @@ edges and nodes: numpy's sums do not run in the device's order, and the library 
                         the analytic blocks.
   consistent()          edges built from a truth, nodes started 1 degree / 3 % / 0.05 off: the minimum is the truth, cost 0.
   drifting()            a circular track with 1 % scale drift per frame and 0.004 rad of rotation noise per pair, one loop edge.
+  star()                every edge at one hub, in both directions and many per pair, every measurement noisy: the minimum costs > 0.
+  weighted(), perturbed()  an item with per-edge, per-group weights from [0.25, 4]; with every measurement moved off the truth's.
+
+At a minimum with cost > 0 the 2^-40 stop rule and the CG tolerance leave the nodes determined to about 1e-8 only, and two correct
+implementations may take different numbers of CG iterations.  FLOW takes the flow out of the comparison: under cg_tolerance = 1e-30
+and small caps every solve runs exactly cg_iterations and the outer loop exactly max_iterations, and what is left between two
+implementations is rounding (DELTA_FLOW).  info["cg_ratio"] (rho' / rho_0 at each solve's exit) says that the conjugate gradient was
+still far above its rounding floor when it was cut: past convergence it only amplifies noise.
 """
 import numpy as np
 
@@ -21,6 +29,18 @@ JACOBIAN_BOUND = 4 * JACOBIAN_WORST
 DELTA_REF = 1.2e-14          # measured over CONSISTENT_CASES: 1.11e-14 between optimize() and second_formulation()
 DRIFT_WORST = 0.092          # measured over DRIFT_CASES: the worst (centre error after) / (centre error before), 0.0918
 DRIFT_BOUND = 0.5            # the issue's
+FLOW = dict(cg_tolerance=1e-30)   # with max_iterations in 1 .. 3 and a small cg_iterations: both loops run exactly to their caps
+FLOW_RATIO = 1e-4            # a fixed-flow case is valid when every solve ends at its cap with rho' / rho_0 >= this
+CONVERGED = dict(max_iterations=64, cg_iterations=2048, cg_tolerance=1e-8)
+DELTA_FLOW = 5.4e-15         # measured over graph_cases.LOOP_CASES under their fixed flow: 5.33e-15 between optimize() and the serial walk
+# Run to convergence, two correct implementations agree to rounding while their flows coincide and to about 1e-8 sqrt(cost) once one
+# of them takes another number of CG iterations: measured between optimize() and the serial walk over graph_cases.CONVERGED_CASES
+# and WEIGHT_CASES, 4.13e-9 on weighted_drift(16, 2) (848 against 1312 CG iterations) and at most 6.0e-12 on the others
+CONVERGED_NODES = 4.2e-9
+CONVERGED_COST = 5.0e-15     # over the same cases: 4.996e-15, the final cost's relative difference
+WEIGHT_WORST = 6.4e-8        # measured over WEIGHT_CASES: 6.33e-8 between optimize() and second_formulation(); unit weights end >= 3.3e-2 away
+WEIGHT_BOUND = 16 * WEIGHT_WORST
+WEIGHT_CASES = [(n, s) for n in (16, 48) for s in range(3)]   # drifting(N, seed, extra=((N // 2, 1),)) under weighted(seed)
 
 JACOBIAN_CASES = list(range(20))
 CONSISTENT_CASES = [(n, l, s) for n, l in ((2, 0), (3, 1), (5, 2), (64, 2)) for s in (0, 1, 2, 4)]   # N, loops, seed
@@ -160,7 +180,7 @@ def optimize(scale, R, T, fixed, n_nodes, ab, zs, zR, zt, zw, n_edges, **prm):
     N, E = int(n_nodes), int(n_edges)
     nan = float("nan")
     stats = np.array([0.0, nan, nan, nan])
-    info = dict(written=np.zeros(S, bool), cg=[], cg_capped=False, lm_capped=False, moved=False)
+    info = dict(written=np.zeros(S, bool), cg=[], cg_ratio=[], cg_capped=False, lm_capped=False, moved=False, steps=0, accepted=0)
     if N < 1 or N > S or E < 0 or E > Es:
         return scale, R, T, stats, info
     zs, zR, zt, zw = (np.asarray(v, np.float64) for v in (zs, zR, zt, zw))
@@ -184,6 +204,7 @@ def optimize(scale, R, T, fixed, n_nodes, ab, zs, zR, zt, zw, n_edges, **prm):
     lam, accepted = LAMBDA0, 0
     stopped = False
     for _ in range(p["max_iterations"]):
+        info["steps"] += 1
         r = residuals(s[a], Rm[a], t[a], s[b], Rm[b], t[b], zs, zR, zt)
         Ja, Jb = jacobians(s[a], Rm[a], t[a], s[b], Rm[b], t[b], zs, zR, zt)
         H, g = np.zeros((N, 7, 7)), np.zeros((N, 7))
@@ -215,6 +236,7 @@ def optimize(scale, R, T, fixed, n_nodes, ab, zs, zR, zt, zw, n_edges, **prm):
                 stopped = True
                 break
     info["lm_capped"] = not stopped
+    info["accepted"] = accepted
     if accepted == 0:
         return scale, R, T, stats, info
     s1, s2 = obj0 / stats[0], obj / stats[0]
@@ -256,7 +278,7 @@ def _pcg(H, g, damp, active, Ja, Jb, W, a, b, p, info):
     z = prec(r)
     pv = z.copy()
     rho = rho0 = float(np.sum(r * z))
-    it = 0
+    it, last = 0, rho
     for it in range(1, p["cg_iterations"] + 1):
         q = op(pv)
         pq = float(np.sum(pv * q))
@@ -269,7 +291,7 @@ def _pcg(H, g, damp, active, Ja, Jb, W, a, b, p, info):
         x = x + alpha * pv
         r = r - alpha * q
         z = prec(r)
-        new = float(np.sum(r * z))
+        new = last = float(np.sum(r * z))
         if new <= p["cg_tolerance"] * rho0:
             break
         if it == p["cg_iterations"]:
@@ -278,6 +300,7 @@ def _pcg(H, g, damp, active, Ja, Jb, W, a, b, p, info):
         pv = z + (new / rho) * pv
         rho = new
     info["cg"].append(it)
+    info["cg_ratio"].append(last / rho0)
     return x, True
 
 
@@ -417,15 +440,87 @@ def drifting(N, seed, extra=()):
     return pack(nodes, edges, [0]), truth
 
 
+def noisy(Z, rng, rot=0.004, trans=0.02, scale=0.01):
+    """a measurement moved off: about `rot` rad, `trans` and `scale` relative"""
+    return Z[0] * (1.0 + scale * rng.normal()), random_rotation(rng, rot * rng.uniform(0.5, 1.5)) @ Z[1], Z[2] + trans * rng.normal(size=3)
+
+
+def star(N, hub, E, seed, leaves, ring=0, node_stride=None, edge_stride=None):
+    """E edges, every one between `hub` (free) and one of `leaves` in turn, written (hub, leaf) and (leaf, hub) alternately, so
+    every pair has many edges in both directions when E > len(leaves) -- but the last `ring` edges, which join each leaf to the next
+    (without them block-Jacobi all but solves a star, and the conjugate gradient is at its floor after two iterations); every
+    measurement noisy(); node 0 held at the truth, the others started 1 degree / 3 % / 0.05 off; a node that is neither the hub nor
+    a leaf has no edge -> (item, truth nodes)"""
+    rng = np.random.default_rng(9000 * N + seed)
+    truth = [(float(rng.uniform(0.8, 1.25)), random_rotation(rng, rng.uniform(0.0, 1.0)), 3.0 * rng.normal(size=3)) for _ in range(N)]
+    edges = []
+    for k in range(E):
+        leaf = leaves[k % len(leaves)]
+        a, b = (hub, leaf) if (k + k // len(leaves)) % 2 else (leaf, hub)
+        if k >= E - ring:
+            a, b = leaf, leaves[(k + 1) % len(leaves)]
+        edges.append((a, b, noisy(relative(truth[a], truth[b]), rng)))
+    nodes = [truth[0]]
+    for s, R, t in truth[1:]:
+        d = rng.normal(size=3)
+        nodes.append((s * (1.0 + 0.03 * rng.choice([-1.0, 1.0])), random_rotation(rng, np.radians(1.0)) @ R, t + 0.05 * d / np.linalg.norm(d)))
+    return pack(nodes, edges, [0], node_stride, edge_stride), truth
+
+
+def _copy(it):
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in it.items()}
+
+
+def weighted_drift(N, seed):
+    """drifting(N, seed) with one more loop N // 2 -> 1 (both loops are written from the later frame to the earlier one), weighted
+    -> (item, truth nodes)"""
+    it, truth = drifting(N, seed, extra=((N // 2, 1),))
+    return weighted(it, N + seed), truth
+
+
+def weighted(it, seed, zero=None):
+    """a copy of the item with every edge's three weights drawn from [0.25, 4] (2^u, u uniform); zero = (edge, group) sets that one to 0"""
+    it = _copy(it)
+    E = int(it["n_edges"])
+    it["zw"][:E] = 2.0 ** np.random.default_rng(31337 + seed).uniform(-2.0, 2.0, (E, 3))
+    if zero is not None:
+        it["zw"][zero] = 0.0
+    return it
+
+
+def perturbed(it, seed, rot=0.004, trans=0.02, scale=0.01):
+    """a copy of the item with every measurement moved off: about `rot` rad, `trans`, `scale` relative"""
+    it = _copy(it)
+    E = int(it["n_edges"])
+    rng = np.random.default_rng(4242 + seed)
+    ax = rng.normal(size=(E, 3))
+    w = (rot * rng.uniform(0.5, 1.5, E))[:, None] * ax / np.linalg.norm(ax, axis=1, keepdims=True)
+    it["zR"][:E] = (rotate(w, np.eye(3)) @ it["zR"][:E].reshape(E, 3, 3)).reshape(E, 9)
+    it["zs"][:E] *= 1.0 + scale * rng.normal(size=E)
+    it["zt"][:E] += trans * rng.normal(size=(E, 3))
+    return it
+
+
+def group_weights(it):
+    """(N, 3): each node's weight per group summed over its usable edges"""
+    N, E = int(it["n_nodes"]), int(it["n_edges"])
+    use = usable_edges(N, E, it["fixed"], it["ab"], it["zs"], it["zR"], it["zt"], it["zw"])
+    out = np.zeros((N, 3))
+    for side in (0, 1):
+        np.add.at(out, np.asarray(it["ab"])[:E][use, side], it["zw"][:E][use])
+    return out
+
+
 def centre_error(T, truth):
     return float(max(np.linalg.norm(T[i] - truth[i][2]) for i in range(len(truth))))
 
 
 # ------------------------------------------------------------------------------------------------ on the world
-def close_loops(tracks, loops, seq_weight=(1.0, 1.0, 1.0), loop_weight=(1.0, 1.0, 1.0), **prm):
+def close_loops(tracks, loops, seq_weight=(1.0, 1.0, 1.0), loop_weight=(1.0, 1.0, 1.0), infos=None, **prm):
     """vslam_world_close_loops restated.  tracks: a list of dict(Twc (F, 16) f64, pose (F, 16) f32, scale (F,), carry (K, 3),
     carry_index (K,), points (cap, 4) f32, size, anchor (cap,) the frame of each point's first observation or -1) -- changed IN PLACE
-    --; loops: a list of (track, frame_a, frame_b, use, s, R (9,), t (3,)).  -> [stats (4,) per track], [written (F,) per track]"""
+    --; loops: a list of (track, frame_a, frame_b, use, s, R (9,), t (3,)); infos: a list that takes optimize()'s info of every
+    track with a taken loop.  -> [stats (4,) per track], [written (F,) per track]"""
     all_stats, all_written = [], []
     for ti, tr in enumerate(tracks):
         F = len(tr["Twc"])
@@ -453,6 +548,8 @@ def close_loops(tracks, loops, seq_weight=(1.0, 1.0, 1.0), loop_weight=(1.0, 1.0
         it = pack(nodes, edges, [0])
         it["zw"][:] = np.asarray(wts, np.float64)
         s, R, T, stats, info = optimize(*args(it), **prm)
+        if infos is not None:
+            infos.append(info)
         wr = info["written"]
         all_stats.append(stats)
         all_written.append(wr.copy())

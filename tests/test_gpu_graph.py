@@ -2,7 +2,9 @@
 graph_math.h (tests/native/graph_serial.cpp) and tests/ref_graph.py.  The number of usable edges, the set of written nodes and
 every bit outside it (the padding's sentinels included) are exact; the written nodes are held within 16 x ref_graph.DELTA_REF of the
 serial walk and of the reference.  The shapes (graph_cases.SHAPES) put the 256 lanes on both sides of N and E and take several
-strided passes; every one converges before either iteration cap (test_ref_graph.py asserts that)."""
+strided passes; every one converges before either iteration cap (test_ref_graph.py asserts that).  Every graph here is consistent
+(cost 0 at the minimum) and unit-weighted, and the one world scene carries a loop 2e-4 off: loops that disagree with the chain,
+weights that differ, multi-edges, the capacity and both iteration caps are tests/test_gpu_graph_loops.py's."""
 import ctypes as C
 
 import numpy as np
